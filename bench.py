@@ -21,6 +21,11 @@ use_gpu=True)`` — one worker actor per GPU, RCCL rendezvous, exactly the "8 Ra
 BASELINE config #2 (reference ray-jobs/pytorch_llm_ray.py:346-350,368-376) — and never touches the
 GPU itself. ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`` also works;
 a ``WORLD_SIZE`` that disagrees with ``--gpus`` is an error. Rank 0 prints ONE JSON line.
+
+A run does only what its headline figure needs: set-up, ``--warmup`` steps, ``--steps`` timed steps,
+the JSON line. ``--dump-outputs DIR`` adds the last timed step's results as ``.npy`` files (after the
+timed region), for comparing two builds on the same seeded inputs. Anything further the benchmark
+comes to measure belongs behind ``--full``; today that option adds nothing.
 """
 from __future__ import annotations
 
@@ -104,6 +109,15 @@ def parse():
                          "'<model>[N/L layers]', so it is never mistaken for the full model's number)")
     ap.add_argument("--plan-only", action="store_true",
                     help="print the per-rank HBM / host memory plan (parallel/planner.py) for this config and exit")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step computed as DIR/<name>.npy "
+                         "(float32): loss, grad_norm and params_sample, a fixed seeded sample of the updated "
+                         "parameters. Inputs, weights and the sample are seeded, so two builds run with the same "
+                         "arguments can be compared file by file")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure. There is nothing "
+                         "of that kind today: every run is the plain set-up / warm-up / timed steps / one JSON "
+                         "line, and further configurations are separate runs chosen by the options above")
     ap.add_argument("--launcher", default="", help=argparse.SUPPRESS)  # set by launch_workers
     return ap.parse_args()
 
@@ -172,6 +186,32 @@ def _link_plan(plan, a, step_s):
     return host_link_plan(plan, a.resident_fraction, step_s)
 
 
+DUMP_SAMPLE_ELEMS = 1 << 22  # params_sample.npy: 16 MiB of float32, whatever the model size
+DUMP_SAMPLE_SEED = 20240531
+
+
+def _dump_outputs(path, loss, grad_norm, named_tensors):
+    """``--dump-outputs``: the last timed step's results as float32 ``.npy`` files. ``named_tensors``
+    are the parameters the step updated, in a fixed order; of each, a share of DUMP_SAMPLE_ELEMS in
+    proportion to its size is kept, at positions drawn from a generator with a fixed seed (all of it
+    when the whole set is smaller), so the same positions are read in every run of the same model."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.asarray([loss], dtype=np.float32))
+    np.save(os.path.join(path, "grad_norm.npy"), np.asarray([grad_norm], dtype=np.float32))
+    total = sum(t.numel() for _, t in named_tensors)
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    parts = []
+    with torch.no_grad():
+        for _, t in named_tensors:
+            flat, n = t.detach().reshape(-1), t.numel()
+            if total > DUMP_SAMPLE_ELEMS:
+                k = min(n, max(1, n * DUMP_SAMPLE_ELEMS // total))
+                idx = torch.from_numpy(np.sort(rng.integers(0, n, size=k))).to(flat.device)
+                flat = flat[idx]
+            parts.append(flat.float().cpu().numpy())
+    np.save(os.path.join(path, "params_sample.npy"), np.concatenate(parts) if parts else np.zeros(0, np.float32))
+
+
 def _bench_worker(cfg: dict):
     """TorchTrainer ``train_loop_per_worker``: the process group is already up (TrainWorker)."""
     run(argparse.Namespace(**cfg))
@@ -209,6 +249,8 @@ def launch_workers(a) -> int:
 
 def main():
     a = parse()
+    if a.dump_outputs:  # the rank that writes may run in a worker with another working directory
+        a.dump_outputs = os.path.abspath(a.dump_outputs)
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None:
         if int(env_world) != a.gpus:
@@ -386,6 +428,7 @@ def run(a):
 
     fsdp = a.parallel == "fsdp"
     counter = [0]
+    last_clip = [None]
     from gke_ray_train_amd.observability import StepMeter
     meter = None
     if a.metrics_jsonl:
@@ -415,6 +458,7 @@ def run(a):
             eng.finish_gradient_sync()
         with ph("optimizer"):
             st = eng.clip_grad_norm_(a.max_grad_norm)  # global norm of the averaged gradient, on device
+            last_clip[0] = st  # --dump-outputs reads the last step's norm after the timed region
             opt.step(grad_scale=st)
             if not fsdp:
                 eng.after_optimizer_step()  # ZeRO: async all-gather of the updated shards
@@ -488,6 +532,13 @@ def run(a):
         (f"+sp{a.sp}" if a.sp > 1 else "") + ("+zero1" if getattr(eng, "zero", False) else "") + \
         ("+offload" if a.offload else "") + \
         ("" if a.peft == "none" else f"+{a.peft}")
+    if rank == 0 and a.dump_outputs:
+        # the device is idle here (synchronised above), so every update of the last step has landed
+        if fsdp:  # this rank's parameter shards and the replicated parameters, as the optimizer holds them
+            named = [("shard_store", eng.shard_store), ("rep_flat", eng.rep_flat)]
+        else:
+            named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        _dump_outputs(a.dump_outputs, float(loss.item()) * accum, float(last_clip[0].buf[0].item()), named)
     if rank == 0:
         out = {
             "metric": _baseline_metric(),

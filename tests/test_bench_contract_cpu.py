@@ -74,6 +74,34 @@ def test_bench_one_gpu_stays_in_process(tmp_path):
     assert out["n_gpus"] == 1 and out["launcher"] == "in-process" and out["config"]["parallelism"] == "dp1"
 
 
+def test_bench_dump_outputs_repeatable_and_full_flag(tmp_path):
+    """``--dump-outputs DIR``: float32 .npy files of the last timed step (loss, grad norm, a seeded
+    sample of the updated parameters), the same from run to run with the same arguments; ``--full``
+    is accepted and leaves the result line's keys and the computed values as they are."""
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+            "--model", "llama-tiny-gqa", "--device", "cpu", "--seq", "64", "--batch", "2"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["OMP_NUM_THREADS"] = "2"
+    outs, dumps = [], []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        r = subprocess.run(base + ["--dump-outputs", name] + extra, cwd=str(tmp_path), env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:]
+        outs.append(_json_line(r.stdout))
+        d = tmp_path / name
+        assert sorted(os.listdir(d)) == ["grad_norm.npy", "loss.npy", "params_sample.npy"]
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    assert set(outs[0]) == set(outs[1]) and outs[0]["steps"] == 2
+    for k, v in dumps[0].items():
+        assert v.dtype == np.float32 and v.size > 0 and np.isfinite(v).all(), k
+        assert v.shape == dumps[1][k].shape, k
+        np.testing.assert_allclose(v, dumps[1][k], rtol=1e-5, atol=1e-7, err_msg=k)
+    assert dumps[0]["loss"].shape == (1,) and abs(float(dumps[0]["loss"][0]) - outs[0]["loss"]) < 1e-3
+    assert float(dumps[0]["grad_norm"][0]) > 0
+    assert sum(v.nbytes for v in dumps[0].values()) <= 64 << 20
+
+
 def test_bench_world_size_mismatch_is_an_error(tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
            "--model", "llama-tiny-gqa", "--device", "cpu"]
