@@ -190,7 +190,7 @@ struct AttnParams {
   // workgroup schedule of one bf16 kernel, set by the launchers from the attn_set_schedule() mask
   // (1 = forward, 2 = dQ, 4 = dK / dV): 0 = one block per workgroup, heaviest first; 1 = causal pairs
   int sched;
-  // set by the launchers (attn_set_dma_fast, GRT_ATTN_DMA_FAST, default 1): tiles that lie inside the
+  // set by the launchers (attn_set_dma_fast, default 1): tiles that lie inside the
   // sequence take their LDS-DMA source addresses as a uniform tile base + per-lane offsets fixed for
   // the sweep (one 64-bit add per DMA) instead of the clamped per-lane row arithmetic
   int dma_fast;
@@ -348,7 +348,6 @@ struct GemvFused {
   int rope_S, cache_L, hq, hkv;
 };
 void gemv_fused_bf16(const GemvFused& f, hipStream_t s);
-int gemv_k_split(int N);
 int gemv_workgroups(int N);
 
 // ---------------- xGMI peer-to-peer collectives (ipc_comm.hip) ----------------

@@ -820,7 +820,8 @@ __global__ __launch_bounds__(K2NT, 1) void attn_bwd_dkdv_kernel(const AttnBwdPar
   }
 }
 
-// dK / dV, wave-pair form (default without dropout; GRT_ATTN_DKDV=1 selects the 4-wave kernel above). The
+// dK / dV, wave-pair form (default without dropout; attn_set_dkdv_form(1) selects the 4-wave kernel
+// above, which also takes every dropout launch). The
 // 4-wave kernel holds K, V, dK^T and dV^T of its 32 keys in one wave (~440 registers: one wave per
 // SIMD, nothing covers its exponentials, LDS reads and barrier; 25 % MFMA busy,
 // profiles/r3_pmc_kernel_zoo.md). Here the work of 32 keys is split over a wave PAIR on one SIMD
@@ -834,7 +835,7 @@ __global__ __launch_bounds__(K2NT, 1) void attn_bwd_dkdv_kernel(const AttnBwdPar
 // The dP-wave lags one tile, so the ring keeps the previous tile's Q image resident: 5 slots, DMA
 // three tiles ahead (slot of tile t + 3 = slot of tile t - 2). P crosses LDS as fp32 (the numerics
 // of the 4-wave kernel), double-buffered by tile parity. One barrier per tile, plus one after the
-// sweep for the dP-wave's last tile. Same masks, dropout hash, RoPE epilogue and schedule.
+// sweep for the dP-wave's last tile. Same masks, RoPE epilogue and schedule.
 constexpr int K3N = 128, K3M = 32, K3NT = 512, K3NS = 5, K3PD = K3NS - 2;
 constexpr int K3IMG = K3M * D * 2;                // one 32-row image: 8 KiB
 constexpr int K3SLOT = 2 * K3IMG + 8 * 1024;      // Q image, dO image, 8 per-wave statistics copies
@@ -842,7 +843,6 @@ constexpr int K3XW = 64 * 16 * 4;                 // one wave's P tile: 64 lanes
 constexpr int K3X = 4 * K3XW;                     // the 4 pairs
 constexpr int K3LDS = K3NS * K3SLOT + 2 * K3X;    // 120 + 32 = 152 KiB
 
-template <bool DROP>
 __global__ __launch_bounds__(K3NT, 1) void attn_bwd_dkdv2_kernel(const AttnBwdParams P) {
   const AttnParams& p = P.f;
   __shared__ __attribute__((aligned(16))) char smem[K3LDS];
@@ -901,7 +901,7 @@ __global__ __launch_bounds__(K3NT, 1) void attn_bwd_dkdv2_kernel(const AttnBwdPa
   const int qmask = (k0 + K3N > sk) ? INT_MAX : (p.causal ? kw0 + 31 - off : INT_MIN);
   // query tiles ending at or before dead_q hold no query at or past this pair's first key: every
   // (query, key) of theirs is masked (causal), and with keys past sk the tile is masked anyway
-  const int dead_q = p.skip_dead && p.causal && !DROP ? kw0 - off : INT_MIN;
+  const int dead_q = p.skip_dead && p.causal ? kw0 - off : INT_MIN;
 
   // LDS-DMA of a tile: wave w fills image rows 4w .. 4w+3 of Q and of dO (one 1-KiB piece each)
   // and its own copy of the tile's 32 lse2 and 32 delta values (3 instructions per wave and tile)
@@ -951,12 +951,7 @@ __global__ __launch_bounds__(K3NT, 1) void attn_bwd_dkdv2_kernel(const AttnBwdPa
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int r = 4 * q + j;
-        if (DROP) {
-          const float z = drop_factor(p, (uint32_t)(b * p.Hq + hkv * grp + prv_h), prv_q + 8 * q + 4 * h + j, mykey);
-          ds[r] = pv[j] * (dpc[r] * z - de[j]);
-        } else {
-          ds[r] = pv[j] * (dpc[r] - de[j]);
-        }
+        ds[r] = pv[j] * (dpc[r] - de[j]);
       }
     }
     const bf16x8 sb0 = pack8(ds, 0), sb1 = pack8(ds, 8);
@@ -1010,10 +1005,7 @@ __global__ __launch_bounds__(K3NT, 1) void attn_bwd_dkdv2_kernel(const AttnBwdPa
         for (int j = 0; j < 4; ++j) pv[j] = fast_exp2(fmaf(s[4 * q + j], c, -ls[j]));
         *reinterpret_cast<f32x4*>(xo + (q * 64 + lane) * 4) = pv;
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-          s[4 * q + j] = DROP ? pv[j] * drop_factor(p, (uint32_t)(b * p.Hq + hkv * grp + cur_h),
-                                                    cur_q + 8 * q + 4 * h + j, mykey)
-                              : pv[j];  // dV uses the dropped probabilities
+        for (int j = 0; j < 4; ++j) s[4 * q + j] = pv[j];
       }
       const bf16x8 pb0 = pack8(s, 0), pb1 = pack8(s, 8);
       __builtin_amdgcn_sched_barrier(0);
@@ -1330,18 +1322,11 @@ __global__ __launch_bounds__(Q2NT, 2) void attn_bwd_dq_kernel(const AttnBwdParam
 
 namespace {
 // bit mask of the kernels that use the causal-pair schedule: 1 = forward, 2 = dQ, 4 = dK / dV
-// (-1: not set yet -> GRT_ATTN_SCHED, default 7: all three kernels pair when the paired grid fills
-// the chip; B8 S1024 H32: forward -10 %, backward -6 %: profiles/r3_attn_schedule.md)
-int g_sched = -1;
-// dK / dV kernel: 2 = wave-pair (default), 1 = the 4-wave kernel (GRT_ATTN_DKDV, attn_set_dkdv_form)
-int g_dkdv = -1;
-int dkdv_form() {
-  if (g_dkdv < 0) {
-    const char* e = getenv("GRT_ATTN_DKDV");
-    g_dkdv = e && atoi(e) == 1 ? 1 : 2;
-  }
-  return g_dkdv;
-}
+// (attn_set_schedule; default 7: all three kernels pair when the paired grid fills the chip;
+// B8 S1024 H32: forward -10 %, backward -6 %: profiles/r3_attn_schedule.md)
+int g_sched = 7;
+// dK / dV kernel without dropout: 2 = wave-pair (default), 1 = the 4-wave kernel (attn_set_dkdv_form)
+int g_dkdv = 2;
 int g_skip_dead = -1;
 int skip_dead_now() {
   if (g_skip_dead < 0) {
@@ -1350,27 +1335,13 @@ int skip_dead_now() {
   }
   return g_skip_dead;
 }
-int g_dma_fast = -1;
-int dma_fast_now() {
-  if (g_dma_fast < 0) {
-    const char* e = getenv("GRT_ATTN_DMA_FAST");
-    g_dma_fast = e && atoi(e) == 0 ? 0 : 1;
-  }
-  return g_dma_fast;
-}
+int g_dma_fast = 1;  // attn_set_dma_fast
 // the fast addressing keeps per-lane row offsets in 32 bits (24-bit multiplies): every row stride
 // of the streamed operands must be below 2^24 elements
 int dma_fast_for(const AttnParams& p, int64_t do_ss) {
   const int64_t lim = (int64_t)1 << 24;
-  return dma_fast_now() && p.q_ss < lim && p.k_ss < lim && p.v_ss < lim && do_ss < lim && p.q_ss >= 0 &&
+  return g_dma_fast && p.q_ss < lim && p.k_ss < lim && p.v_ss < lim && do_ss < lim && p.q_ss >= 0 &&
          p.k_ss >= 0 && p.v_ss >= 0 && do_ss >= 0;
-}
-int sched_now() {
-  if (g_sched < 0) {
-    const char* e = getenv("GRT_ATTN_SCHED");
-    g_sched = e ? atoi(e) : 7;
-  }
-  return g_sched;
 }
 }  // namespace
 
@@ -1392,15 +1363,15 @@ static int pair_if_fills(int want, int nblk, int groups, int per_cu) {
 
 void attn_set_schedule(int s) { g_sched = s; }
 void attn_set_dkdv_form(int f) { g_dkdv = f == 1 ? 1 : 2; }
-int attn_get_dkdv_form() { return dkdv_form(); }
+int attn_get_dkdv_form() { return g_dkdv; }
 void attn_set_dma_fast(int on) { g_dma_fast = on ? 1 : 0; }
 void attn_set_skip_dead(int on) { g_skip_dead = on ? 1 : 0; }
-int attn_get_schedule() { return sched_now(); }
+int attn_get_schedule() { return g_sched; }
 
 // Padding-free packing (cu_seqlens): the grid is sized for the longest sequence, so a shorter one's
 // heavy block of a causal pair exits at once and the pair's work is no longer equal — pairs off
 // (LoRA step at 6656 packed tokens 33.1 -> 31.4 ms per 1K tokens; profiles/r3_varlen_attention.md).
-static int sched_for(const AttnParams& p, int bit) { return p.cu_seqlens ? 0 : (sched_now() >> bit) & 1; }
+static int sched_for(const AttnParams& p, int bit) { return p.cu_seqlens ? 0 : (g_sched >> bit) & 1; }
 
 void attn_fwd(const AttnParams& p0, hipStream_t s) {
   AttnParams p = p0;
@@ -1435,13 +1406,11 @@ void attn_bwd(const AttnBwdParams& p0, hipStream_t s) {
   // the wave-pair form: B8 S1024 H32 backward 425 -> 412 us, GQA 32:8 even; with probability
   // dropout it is slower (142 -> 150 us at B2 S1024 p 0.1: the dP-wave recomputes the keep hash the
   // S-wave already drew), so dropout keeps the 4-wave kernel (tools/attn_dkdv_ab.py, profiles/r4_attention.md)
-  const bool pair = dkdv_form() == 2 && !p.f.drop_thresh;
   if (p.f.drop_thresh) {
-    if (pair) hipLaunchKernelGGL(attn_bwd_dkdv2_kernel<true>, g1, dim3(K3NT), 0, s, pk);
-    else hipLaunchKernelGGL(attn_bwd_dkdv_kernel<true>, g1, dim3(K2NT), 0, s, pk);
+    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<true>, g1, dim3(K2NT), 0, s, pk);
     hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, g2, dim3(Q2NT), 0, s, pq);
   } else {
-    if (pair) hipLaunchKernelGGL(attn_bwd_dkdv2_kernel<false>, g1, dim3(K3NT), 0, s, pk);
+    if (g_dkdv == 2) hipLaunchKernelGGL(attn_bwd_dkdv2_kernel, g1, dim3(K3NT), 0, s, pk);
     else hipLaunchKernelGGL(attn_bwd_dkdv_kernel<false>, g1, dim3(K2NT), 0, s, pk);
     hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, g2, dim3(Q2NT), 0, s, pq);
   }

@@ -25,8 +25,6 @@
 // projection: every workgroup re-read row, residual and weight from L2) and a last-workgroup
 // reduction behind a device-scope counter (+22-30 us: the release / acquire fences write back and
 // invalidate the whole L2 in every workgroup).
-#include <stdlib.h>
-
 #include "grt_common.h"
 #include "grt_kernels.h"
 
@@ -34,6 +32,10 @@ namespace grt {
 namespace {
 
 constexpr int kR = 4;  // weight rows per wave
+// K split over the workgroup's 4 waves at every N: Llama-3.1-8B decode gate_up 41.3 -> 35.2 us,
+// lm_head 165 -> 149 us (7.1 TB/s), the small projections as before (tools/gemv_bench.py,
+// profiles/r5_decode.md)
+constexpr int kKS = 4;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void bf16x8_to_f32(const u32x4& v, float (&f)[8]) {
@@ -313,37 +315,21 @@ __global__ __launch_bounds__(64 * KS) void gemv_mfma_kernel(const bf16* __restri
   }
 }
 
-template <int KS, int PRO, int EPI>
+template <int PRO, int EPI>
 void launch_gemv(const GemvArgs& a, int M, hipStream_t s) {
   const dim3 grid((unsigned)gemv_workgroups(a.N));
   switch (M) {
-    case 1: hipLaunchKernelGGL((gemv_kernel<1, KS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((gemv_kernel<2, KS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((gemv_kernel<3, KS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((gemv_kernel<4, KS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((gemv_kernel<1, kKS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((gemv_kernel<2, kKS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((gemv_kernel<3, kKS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((gemv_kernel<4, kKS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
   }
-}
-
-template <int PRO, int EPI>
-void launch_ks(const GemvArgs& a, int M, hipStream_t s) {
-  if (gemv_k_split(a.N) == 4) launch_gemv<4, PRO, EPI>(a, M, s);
-  else launch_gemv<1, PRO, EPI>(a, M, s);
 }
 
 }  // namespace
 
-int gemv_k_split(int N) {
-  static const int env = [] { const char* e = getenv("GRT_GEMV_KSPLIT"); return e ? atoi(e) : -1; }();
-  if (env == 1 || env == 4) return env;
-  (void)N;
-  // K split over the workgroup's 4 waves at every N: Llama-3.1-8B decode gate_up 41.3 -> 35.2 us,
-  // lm_head 165 -> 149 us (7.1 TB/s), the small projections as before (tools/gemv_bench.py,
-  // profiles/r5_decode.md)
-  return 4;
-}
-
 int gemv_workgroups(int N) {
-  const int rows_per_wg = (4 / gemv_k_split(N)) * kR;
+  const int rows_per_wg = (4 / kKS) * kR;
   return (N + rows_per_wg - 1) / rows_per_wg;
 }
 
@@ -365,8 +351,8 @@ void gemv_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, 
   GemvArgs a{};
   a.x = static_cast<const bf16*>(x), a.ldx = ldx, a.w = static_cast<const bf16*>(w), a.y = static_cast<bf16*>(y);
   a.ldy = ldy, a.N = N, a.K = K;
-  if (swiglu) launch_ks<PRO_SWI, EPI_NONE>(a, M, s);
-  else launch_ks<PRO_NONE, EPI_NONE>(a, M, s);
+  if (swiglu) launch_gemv<PRO_SWI, EPI_NONE>(a, M, s);
+  else launch_gemv<PRO_NONE, EPI_NONE>(a, M, s);
 }
 
 void gemv_fused_bf16(const GemvFused& f, hipStream_t s) {
@@ -380,14 +366,14 @@ void gemv_fused_bf16(const GemvFused& f, hipStream_t s) {
   a.cosb = f.cosb, a.sinb = f.sinb, a.pos = f.pos, a.rope_S = f.rope_S, a.cache_L = f.cache_L;
   a.hq = f.hq, a.hkv = f.hkv;
   const bool normx = f.sumsq_in != nullptr, resnorm = f.res != nullptr, rope = f.q_out != nullptr;
-  if (rope && normx) launch_ks<PRO_NORMX, EPI_ROPE>(a, f.M, s);
-  else if (rope) launch_ks<PRO_NONE, EPI_ROPE>(a, f.M, s);
-  else if (normx && resnorm) launch_ks<PRO_NORMX, EPI_RESNORM>(a, f.M, s);
-  else if (normx) launch_ks<PRO_NORMX, EPI_NONE>(a, f.M, s);
-  else if (resnorm && f.swiglu) launch_ks<PRO_SWI, EPI_RESNORM>(a, f.M, s);
-  else if (resnorm) launch_ks<PRO_NONE, EPI_RESNORM>(a, f.M, s);
-  else if (f.swiglu) launch_ks<PRO_SWI, EPI_NONE>(a, f.M, s);
-  else launch_ks<PRO_NONE, EPI_NONE>(a, f.M, s);
+  if (rope && normx) launch_gemv<PRO_NORMX, EPI_ROPE>(a, f.M, s);
+  else if (rope) launch_gemv<PRO_NONE, EPI_ROPE>(a, f.M, s);
+  else if (normx && resnorm) launch_gemv<PRO_NORMX, EPI_RESNORM>(a, f.M, s);
+  else if (normx) launch_gemv<PRO_NORMX, EPI_NONE>(a, f.M, s);
+  else if (resnorm && f.swiglu) launch_gemv<PRO_SWI, EPI_RESNORM>(a, f.M, s);
+  else if (resnorm) launch_gemv<PRO_NONE, EPI_RESNORM>(a, f.M, s);
+  else if (f.swiglu) launch_gemv<PRO_SWI, EPI_NONE>(a, f.M, s);
+  else launch_gemv<PRO_NONE, EPI_NONE>(a, f.M, s);
 }
 
 }  // namespace grt

@@ -20,8 +20,6 @@
 // or store; MFMA fragments are read from padded LDS images (a first version loaded the fragments
 // straight from global memory — 32 rows x 32 B per instruction, address-unit bound, 2-4x slower:
 // profiles/r2_perf_experiments.md).
-#include <stdlib.h>
-
 #include "grt_common.h"
 #include "grt_kernels.h"
 
@@ -65,11 +63,11 @@ constexpr int lora_down_lds_bytes() {  // x images + A images; the final reducti
              ? (2 * 32 * TB * (KC + 8) * 2 + 2 * 32 * RB * (KC + 8) * 2) : (4 - TB) * RB * 16 * 64 * 4;
 }
 
-// KC: K chunk (128, or 64 for half the LDS: two workgroups per CU at R = 192).
+// KC: K chunk (128; 64 at R > 192, where the 128-column images exceed the LDS).
 // TB: 32-token tiles per workgroup. The kernel is bound by the A chunk loads from L2 (one [R][KC]
 // chunk per workgroup per chunk: R / 32 times the x bytes at TB = 1; profiles/r2_perf_experiments.md),
 // so TB = 2 halves them per x byte: wave w takes token tile w % TB and k-slice w / TB of each chunk.
-template <int RB, int KC, int TB, int AD = 1>  // R = 32 * RB
+template <int RB, int KC, int TB>  // R = 32 * RB
 __global__ __launch_bounds__(256) void lora_down_kernel(const LoraDownParams P) {
   constexpr int R = 32 * RB;
   constexpr int XS = KC + 8;         // LDS row (bf16): +16 B so b128 fragment reads of 32 rows spread over banks
@@ -122,15 +120,12 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const LoraDownParams P) 
 #pragma unroll
         for (int v = 0; v < NV; ++v) ring[i][u][v] = *reinterpret_cast<const bf16x8*>(src[u] + i * KC + 8 * v);
     }
-  // A chunks AD ahead in registers (GRT_LORA_DOWN_AD selects 1 or 2 at launch: template AD)
-  bf16x8 areg[AD][NA];
+  // the A chunk one ahead in registers
+  bf16x8 areg[NA];
+  if (nch > 0) {
 #pragma unroll
-  for (int d = 0; d < AD; ++d)
-    if (d < nch) {
-#pragma unroll
-      for (int j = 0; j < NA; ++j)
-        areg[d][j] = *reinterpret_cast<const bf16x8*>(asrc + (int64_t)j * (256 / TPA) * P.K + d * KC);
-    }
+    for (int j = 0; j < NA; ++j) areg[j] = *reinterpret_cast<const bf16x8*>(asrc + (int64_t)j * (256 / TPA) * P.K);
+  }
   f32x16 acc[RB];
 #pragma unroll
   for (int i = 0; i < RB; ++i) acc[i] = f32x16{};
@@ -154,14 +149,12 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const LoraDownParams P) 
         // c - 2, which every wave finished before the barrier of chunk c - 1
         bf16* xt = xs + (i & 1) * XIMG;
         bf16* at = as + (i & 1) * AIMG;
-        constexpr int ad = AD;  // register set of chunk c: (c mod AD), c0 a multiple of LD_PF (a multiple of AD)
-        bf16x8(&ar_c)[NA] = areg[i % ad];
 #pragma unroll
-        for (int j = 0; j < NA; ++j) *reinterpret_cast<bf16x8*>(at + (ar + (256 / TPA) * j) * XS + ac) = ar_c[j];
-        if (c + ad < nch) {
+        for (int j = 0; j < NA; ++j) *reinterpret_cast<bf16x8*>(at + (ar + (256 / TPA) * j) * XS + ac) = areg[j];
+        if (c + 1 < nch) {
 #pragma unroll
           for (int j = 0; j < NA; ++j)
-            ar_c[j] = *reinterpret_cast<const bf16x8*>(asrc + (int64_t)j * (256 / TPA) * P.K + (c + ad) * KC);
+            areg[j] = *reinterpret_cast<const bf16x8*>(asrc + (int64_t)j * (256 / TPA) * P.K + (c + 1) * KC);
         }
 #pragma unroll
         for (int u = 0; u < TB; ++u)
@@ -229,7 +222,7 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const LoraDownParams P) 
   }
 }
 
-// ---- lora_down, LDS-DMA form (default for R = 64 / 128 / 192). The register-staged kernel above
+// ---- lora_down, LDS-DMA form (R = 128 / 192). The register-staged kernel above
 // moves every x and A chunk through VGPRs into LDS (ds_write_b128: ~79 B/clk per CU, the A chunk is
 // R / 32 times the x chunk per 32 tokens); here both arrive by LDS-DMA (global_load_lds_dwordx4,
 // 1 KiB per wave-instruction, XOR-swizzled 128-byte rows: conflict-free b128 fragment reads) into a
@@ -563,29 +556,21 @@ bool lora_down_supported(int64_t M, int K, int R, int ldx, uint64_t offset) {
 
 // 32-token tiles per workgroup: 2 from R = 96 on (the A chunk loads dominate: qkv R = 192 72.8 -> 52.2 us,
 // gate_up R = 128 60.4 -> 45.5 us in the LoRA step); 1 at R = 64, where two tiles cost a workgroup
-// slot per CU (62.7 -> 73.5 us; profiles/r3_lora_grad_gemms.md). GRT_LORA_DOWN_TB=1/2 forces one.
-int lora_down_tb(int R) {
-  static const int env = [] { const char* e = getenv("GRT_LORA_DOWN_TB"); return e ? atoi(e) : 0; }();
-  if (env == 1 || env == 2) return env;
-  return R >= 96 ? 2 : 1;
-}
+// slot per CU (62.7 -> 73.5 us; profiles/r3_lora_grad_gemms.md).
+static int lora_down_tb(int R) { return R >= 96 ? 2 : 1; }
 
 // the LDS-DMA kernel takes R = 128 / 192 (the fused gate/up and q/k/v adapters of the SFT job:
 // 57 -> 44 us and 67 -> 53 us at 6144 tokens, tools/lora_kernel_bench.py); at R = 64 the
-// register-staged kernel is as fast or faster (o 34 vs 34 us, down 100 vs 116 us), so it keeps
-// R = 64 unless GRT_LORA_DOWN_DMA=2. GRT_LORA_DOWN_DMA=0: the register-staged kernel everywhere.
-static bool lora_down_dma(int R) {
-  static const int env = [] { const char* e = getenv("GRT_LORA_DOWN_DMA"); return e ? atoi(e) : 1; }();
-  return env != 0 && (R == 128 || R == 192 || (env == 2 && R == 64));
-}
+// register-staged kernel is as fast or faster (o 34 vs 34 us, down 100 vs 116 us), so it keeps R = 64
+static bool lora_down_dma(int R) { return R == 128 || R == 192; }
 
 int lora_down_splits(int64_t M, int K, int R, int cus) {
   if (lora_down_dma(R)) {
-    // 64-token workgroups (R = 64: two 64 KiB workgroups per CU). Splits are chosen by whole rounds
-    // of workgroups: a launch of 1.1 rounds runs as long as 2 (the last workgroups stream a whole
-    // split alone), so the cost is rounds x (chunks per split + the fp32 partial a split writes, ~2
-    // chunks' worth of bytes), minimised over ks = 1 .. 16 with at least 4 chunks (the ring) per split.
-    const int64_t ntb = (M + 63) / 64, slots = (int64_t)cus * (R == 64 ? 2 : 1);
+    // 64-token workgroups, one per CU. Splits are chosen by whole rounds of workgroups: a launch of
+    // 1.1 rounds runs as long as 2 (the last workgroups stream a whole split alone), so the cost is
+    // rounds x (chunks per split + the fp32 partial a split writes, ~2 chunks' worth of bytes),
+    // minimised over ks = 1 .. 16 with at least 4 chunks (the ring) per split.
+    const int64_t ntb = (M + 63) / 64, slots = cus;
     const int nch = K / LDD_KC;
     int best = 1;
     int64_t best_cost = -1;
@@ -609,43 +594,31 @@ int lora_down_splits(int64_t M, int K, int R, int cus) {
 }
 
 void lora_down(const LoraDownParams& p, hipStream_t s) {
+  const dim3 block(256);
   if (lora_down_dma(p.R)) {
-    const dim3 grid((unsigned)(((p.M + 63) / 64) * p.ksplit)), block(256);
+    const dim3 grid((unsigned)(((p.M + 63) / 64) * p.ksplit));
     const bool xd = p.xd != nullptr;
-#define GRT_LDD(RB)                                                                                  \
-  if (xd) hipLaunchKernelGGL((lora_down_dma_kernel<RB, true>), grid, block, 0, s, p);                \
-  else hipLaunchKernelGGL((lora_down_dma_kernel<RB, false>), grid, block, 0, s, p);
-    if (p.R == 64) { GRT_LDD(2) } else if (p.R == 128) { GRT_LDD(4) } else { GRT_LDD(6) }
-#undef GRT_LDD
+    if (p.R == 128) {
+      if (xd) hipLaunchKernelGGL((lora_down_dma_kernel<4, true>), grid, block, 0, s, p);
+      else hipLaunchKernelGGL((lora_down_dma_kernel<4, false>), grid, block, 0, s, p);
+    } else {
+      if (xd) hipLaunchKernelGGL((lora_down_dma_kernel<6, true>), grid, block, 0, s, p);
+      else hipLaunchKernelGGL((lora_down_dma_kernel<6, false>), grid, block, 0, s, p);
+    }
   } else {
-  const int tbw = lora_down_tb(p.R);
-  const dim3 grid((unsigned)(((p.M + 32 * tbw - 1) / (32 * tbw)) * p.ksplit)), block(256);
-  // GRT_LORA_DOWN_KC=64: half the LDS per workgroup (two workgroups per CU up to R = 192); measured
-  // neutral on the Llama-2-7B LoRA step (profiles/r2_perf_experiments.md), so 128 by default
-  static const int kc_env = [] { const char* e = getenv("GRT_LORA_DOWN_KC"); return e ? atoi(e) : 0; }();
-  const bool kc64 = kc_env == 64;
-  // GRT_LORA_DOWN_AD=2: A chunks two ahead in registers (R = 64 / 128 / 192 at 128-column chunks)
-  static const int ad_env = [] { const char* e = getenv("GRT_LORA_DOWN_AD"); return e ? atoi(e) : 1; }();
-  const bool ad2 = ad_env == 2 && !kc64;
-#define GRT_LD(N)                                                                               \
-  case N:                                                                                       \
-    if (tbw == 1) {                                                                             \
-      if (kc64) hipLaunchKernelGGL((lora_down_kernel<N, 64, 1>), grid, block, 0, s, p);         \
-      else if (ad2 && (N == 2 || N == 4 || N == 6))                                             \
-        hipLaunchKernelGGL((lora_down_kernel<N, 128, 1, (N == 2 || N == 4 || N == 6) ? 2 : 1>), grid, block, 0, s, p); \
-      else hipLaunchKernelGGL((lora_down_kernel<N, 128, 1>), grid, block, 0, s, p);             \
-    } else { /* R > 192: 64-column chunks (the 128-column images exceed the LDS) */            \
-      if (kc64) hipLaunchKernelGGL((lora_down_kernel<N, 64, 2>), grid, block, 0, s, p);         \
-      else if (ad2 && (N == 2 || N == 4 || N == 6))                                             \
-        hipLaunchKernelGGL((lora_down_kernel<N, (N >= 7 ? 64 : 128), 2, (N == 2 || N == 4 || N == 6) ? 2 : 1>), grid, block, 0, s, p); \
-      else hipLaunchKernelGGL((lora_down_kernel<N, (N >= 7 ? 64 : 128), 2>), grid, block, 0, s, p); \
-    }                                                                                           \
-    break;
-  switch (p.R / 32) {
-    GRT_LD(1) GRT_LD(2) GRT_LD(3) GRT_LD(4) GRT_LD(5) GRT_LD(6) GRT_LD(7)
-    default: GRT_LD(8)
-  }
-#undef GRT_LD
+    // 128-column chunks (64-column chunks, half the LDS per workgroup, measured neutral on the
+    // Llama-2-7B LoRA step: profiles/r2_perf_experiments.md) except at R > 192, where the
+    // 128-column images exceed the LDS
+    const int tbw = lora_down_tb(p.R);
+    const dim3 grid((unsigned)(((p.M + 32 * tbw - 1) / (32 * tbw)) * p.ksplit));
+    switch (p.R / 32) {
+      case 1: hipLaunchKernelGGL((lora_down_kernel<1, 128, 1>), grid, block, 0, s, p); break;
+      case 2: hipLaunchKernelGGL((lora_down_kernel<2, 128, 1>), grid, block, 0, s, p); break;
+      case 3: hipLaunchKernelGGL((lora_down_kernel<3, 128, 2>), grid, block, 0, s, p); break;
+      case 5: hipLaunchKernelGGL((lora_down_kernel<5, 128, 2>), grid, block, 0, s, p); break;
+      case 7: hipLaunchKernelGGL((lora_down_kernel<7, 64, 2>), grid, block, 0, s, p); break;
+      default: hipLaunchKernelGGL((lora_down_kernel<8, 64, 2>), grid, block, 0, s, p); break;  // R = 256
+    }
   }
   if (p.ksplit > 1) {
     const int64_t n4 = p.M * (int64_t)p.R / 4;

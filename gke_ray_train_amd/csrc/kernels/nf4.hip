@@ -115,11 +115,14 @@ __global__ __launch_bounds__(256) void nf4_dequant_t_kernel(const uint8_t* __res
   }
 }
 
-// ---- bf16 dequantisation, v2 (the per-use path of QLoRA without the resident cache) ----------
-// v1 above looks the codes up in __constant__ memory with lane-divergent indices: one vector
-// memory load per weight. v2 maps a whole code BYTE to its two levels through a 256-entry float2
-// table in LDS (one ds_read_b64 per two weights; one 2 KiB table, conflict-free broadcast reads).
-// Blocksize 64 only (the QLoRA format): 16 or 32 consecutive weights of a lane share one absmax.
+// ---- bf16 dequantisation through an LDS table (the per-use path of QLoRA without the resident
+// cache) ----
+// The kernels above look the codes up in __constant__ memory with lane-divergent indices: one
+// vector memory load per weight. They serve fp32 output, blocksize != 64, unaligned output and
+// rows % 64 != 0. The kernels below map a whole code BYTE to its two levels through a 256-entry
+// float2 table in LDS (one ds_read_b64 per two weights; one 2 KiB table, conflict-free broadcast
+// reads). Blocksize 64 only (the QLoRA format): 16 or 32 consecutive weights of a lane share one
+// absmax.
 __device__ __forceinline__ void nf4_lut_init(float2* lut) {
   const int t = threadIdx.x;  // blockDim.x == 256
   lut[t] = make_float2(kNF4[t >> 4], kNF4[t & 15]);
@@ -209,11 +212,6 @@ __global__ __launch_bounds__(256) void nf4_dequant_t2_kernel(const uint8_t* __re
   }
 }
 
-int nf4_version() {
-  static const int v = [] { const char* e = getenv("GRT_NF4_DEQUANT_V1"); return e && atoi(e) == 1 ? 1 : 2; }();
-  return v;
-}
-
 }  // namespace
 
 bool nf4_dequantize_2d(const uint8_t* q, const float* absmax, void* w, int rows, int cols, int64_t ldo,
@@ -228,7 +226,7 @@ bool nf4_dequantize_2d(const uint8_t* q, const float* absmax, void* w, int rows,
 
 void nf4_dequantize_t(const uint8_t* q, const float* absmax, void* wt, int rows, int cols, int blocksize,
                       hipStream_t s) {
-  if (nf4_version() == 2 && blocksize == 64 && rows % 64 == 0 && cols % 128 == 0) {
+  if (blocksize == 64 && rows % 64 == 0 && cols % 128 == 0) {
     const dim3 grid((unsigned)(cols / 128), (unsigned)(rows / 64));
     hipLaunchKernelGGL(nf4_dequant_t2_kernel, grid, dim3(256), 0, s, q, absmax, (bf16*)wt, rows, cols);
     return;
@@ -247,7 +245,7 @@ void nf4_quantize(DType dt, const void* w, uint8_t* q, float* absmax, int64_t n,
 
 void nf4_dequantize(DType dt, const uint8_t* q, const float* absmax, void* w, int64_t n, int blocksize,
                     hipStream_t s) {
-  if (dt == DType::BF16 && nf4_version() == 2 && n < INT32_MAX && reinterpret_cast<uintptr_t>(w) % 16 == 0 &&
+  if (dt == DType::BF16 && n < INT32_MAX && reinterpret_cast<uintptr_t>(w) % 16 == 0 &&
       nf4_dequantize_2d(q, absmax, w, 1, (int)n, n, blocksize, s))
     return;
   int64_t g = (n / 8 + 255) / 256;

@@ -26,33 +26,28 @@ namespace {
 constexpr int kNT = 256;
 constexpr int kSumBlocks = 1024;
 
-template <typename T, int U>
+template <typename T>
 __global__ __launch_bounds__(kNT) void sumsq_kernel(const T* __restrict__ x, int64_t n, float* __restrict__ out) {
   __shared__ float red[kNT / kWave];
   constexpr int V = Vec16<T>::N;
+  constexpr int U = 2;
   const int64_t nv = n / V;
-  float acc = 0.f;
   const int64_t stride = (int64_t)gridDim.x * kNT;
   int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x;
-  // U independent 16-byte loads in flight per lane (one per iteration leaves each wave waiting a full
-  // HBM latency per 1 KiB). Default U = 2: 6.1 TB/s isolated vs 5.7 (U = 4) and 5.6 (U = 1), and the
-  // fastest headline step of the three (scripts/r6/sumsq.sh); GRT_SUMSQ_UNROLL=0 / 4 -> U = 1 / 4
-  if constexpr (U > 1) {
-    float accu[U];
+  // two independent 16-byte loads in flight per lane (one per iteration leaves each wave waiting a
+  // full HBM latency per 1 KiB): 6.1 TB/s isolated vs 5.7 with four loads and 5.6 with one, and the
+  // fastest headline step of the three (profiles/r6_verdict_status.md, profiles/r6_sumsq_box2.txt)
+  float accu[U] = {0.f, 0.f};
+  for (; i + stride < nv; i += U * stride) {
+    float a[U][V];
 #pragma unroll
-    for (int u = 0; u < U; ++u) accu[u] = 0.f;
-    for (; i + (U - 1) * stride < nv; i += U * stride) {
-      float a[U][V];
+    for (int u = 0; u < U; ++u) load16(x + (i + u * stride) * V, a[u]);
 #pragma unroll
-      for (int u = 0; u < U; ++u) load16(x + (i + u * stride) * V, a[u]);
+    for (int u = 0; u < U; ++u)
 #pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int k = 0; k < V; ++k) accu[u] += a[u][k] * a[u][k];
-    }
-    if constexpr (U == 4) acc = (accu[0] + accu[1]) + (accu[2] + accu[3]);
-    else acc = accu[0] + accu[1];
+      for (int k = 0; k < V; ++k) accu[u] += a[u][k] * a[u][k];
   }
+  float acc = accu[0] + accu[1];
   for (; i < nv; i += stride) {
     float a[V];
     load16(x + i * V, a);
@@ -398,23 +393,12 @@ unsigned grid_for(int64_t work) {
 int optim_sumsq_blocks() { return kSumBlocks; }
 
 void sumsq_accumulate(DType dt, const void* x, int64_t n, float* ws, int slot, hipStream_t s) {
-  static const int unroll = [] {
-    const char* e = std::getenv("GRT_SUMSQ_UNROLL");
-    return e && e[0] == '0' ? 1 : e && e[0] == '4' ? 4 : 2;
-  }();
   float* out = ws + (int64_t)slot * kSumBlocks;
   const dim3 g(kSumBlocks), b(kNT);
-  if (dt == DType::BF16) {
-    const bf16* xb = (const bf16*)x;
-    if (unroll == 4) hipLaunchKernelGGL((sumsq_kernel<bf16, 4>), g, b, 0, s, xb, n, out);
-    else if (unroll == 2) hipLaunchKernelGGL((sumsq_kernel<bf16, 2>), g, b, 0, s, xb, n, out);
-    else hipLaunchKernelGGL((sumsq_kernel<bf16, 1>), g, b, 0, s, xb, n, out);
-  } else {
-    const float* xf = (const float*)x;
-    if (unroll == 4) hipLaunchKernelGGL((sumsq_kernel<float, 4>), g, b, 0, s, xf, n, out);
-    else if (unroll == 2) hipLaunchKernelGGL((sumsq_kernel<float, 2>), g, b, 0, s, xf, n, out);
-    else hipLaunchKernelGGL((sumsq_kernel<float, 1>), g, b, 0, s, xf, n, out);
-  }
+  if (dt == DType::BF16)
+    hipLaunchKernelGGL(sumsq_kernel<bf16>, g, b, 0, s, (const bf16*)x, n, out);
+  else
+    hipLaunchKernelGGL(sumsq_kernel<float>, g, b, 0, s, (const float*)x, n, out);
 }
 
 void clip_coef_finalize(const float* ws, int nparts, float max_norm, float prescale, float* out,
@@ -431,10 +415,9 @@ bool adamw_fastmath() {
 template <typename P, typename G, bool FAST>
 void launch_adamw_v(dim3 grid, hipStream_t s, P* p, const G* g, float* m, float* v, float* master, int64_t n,
                     const float* hyper, const float* gsp, uint64_t ioff) {
-  // GRT_ADAMW_V4=1: always the 4-wide variant (A/B switch)
-  static const bool v4 = [] { const char* e = std::getenv("GRT_ADAMW_V4"); return e && e[0] == '1'; }();
+  // 8-wide needs 16-byte-aligned slices; the 4-wide variant is the fallback for 8-byte-aligned ones
   auto a16 = [](const void* q) { return q == nullptr || reinterpret_cast<uintptr_t>(q) % 16 == 0; };
-  if (!v4 && a16(p) && a16(g) && a16(m) && a16(v) && a16(master))
+  if (a16(p) && a16(g) && a16(m) && a16(v) && a16(master))
     hipLaunchKernelGGL((adamw_kernel<P, G, 8, FAST>), grid, dim3(kNT), 0, s, p, g, m, v, master, n, hyper, gsp, ioff);
   else
     hipLaunchKernelGGL((adamw_kernel<P, G, 4, FAST>), grid, dim3(kNT), 0, s, p, g, m, v, master, n, hyper, gsp, ioff);

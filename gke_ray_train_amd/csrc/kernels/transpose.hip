@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16* __restr
   }
 }
 
-// v2: one workgroup = 64 rows x 128 columns (16 KiB). Load: 4 threads per 256-byte row, 16-byte
+// cols % 128 == 0: one workgroup = 64 rows x 128 columns (16 KiB). Load: 4 threads per 256-byte row, 16-byte
 // ds_write_b128 into an XOR-swizzled image (rows of 16 chunks; chunk ^ ((row & 3) << 2 | (row >> 2) & 3),
 // the dual row-write / transposed-read image of gemm.hip). Store: gfx950's ds_read_b64_tr_b16 hands
 // lane i of a 16-lane group column c0 + i of four source rows, so 4 reads give a lane 16 consecutive
@@ -85,12 +85,12 @@ __global__ __launch_bounds__(256) void transpose2_bf16_kernel(const bf16* __rest
 }  // namespace
 
 void transpose_bf16(const void* src, void* dst, int rows, int cols, hipStream_t s) {
-  static const int v1 = [] { const char* e = getenv("GRT_TRANSPOSE_V1"); return e && atoi(e) == 1; }();
-  if (!v1 && cols % 128 == 0) {
+  if (cols % 128 == 0) {
     const dim3 grid((unsigned)(cols / 128), (unsigned)(rows / 64));
     hipLaunchKernelGGL(transpose2_bf16_kernel, grid, dim3(256), 0, s, (const bf16*)src, (bf16*)dst, rows, cols);
     return;
   }
+  // cols % 128 == 64: the 64 x 64 tile kernel
   const dim3 grid((unsigned)(cols / 64), (unsigned)(rows / 64));
   hipLaunchKernelGGL(transpose_bf16_kernel, grid, dim3(256), 0, s, (const bf16*)src, (bf16*)dst, rows, cols);
 }

@@ -48,9 +48,6 @@ DEFAULT_UNITS = ("LlamaDecoderLayer", "EncoderLayer")
 _ALIGN = 64
 
 
-# GRT_FSDP_ZERO_FULL_GRAD=1: memset each unit's whole gradient buffer (A/B switch for the gap-only clear)
-_ZERO_FULL_GRAD = os.environ.get("GRT_FSDP_ZERO_FULL_GRAD", "0") == "1"
-
 class _BwdGather(torch.autograd.Function):
     """Identity on a unit's output; its backward fires right before the unit's backward kernels."""
 
@@ -314,12 +311,9 @@ class FullyShardedDataParallel(nn.Module):
         for p, o, n, s in zip(u.params, u.offsets, u.numels, u.shapes):
             p.data = full[o:o + n].view(s)
 
-    def _acquire(self, n: int, zero: bool = False) -> torch.Tensor:
+    def _acquire(self, n: int) -> torch.Tensor:
         free = self._pool.get(n)
-        buf = free.pop() if free else torch.empty(n, dtype=self.dtype, device=self.device)
-        if zero:
-            buf.zero_()
-        return buf
+        return free.pop() if free else torch.empty(n, dtype=self.dtype, device=self.device)
 
     def _release(self, buf: Optional[torch.Tensor]):
         # Stream safety: the next user of a gather buffer is an all-gather, which RCCL orders after
@@ -453,9 +447,9 @@ class FullyShardedDataParallel(nn.Module):
         # between slots and the tail must be cleared (they must not inject garbage into the
         # reduction): a few small ranges instead of a memset of the whole unit (37 x 55 us per
         # Llama-2-7B step, profiles/r6_proxy8_steps.md)
-        g = self._acquire(u.total, zero=_ZERO_FULL_GRAD)
-        gaps = None if _ZERO_FULL_GRAD else getattr(u, "_grad_gaps", None)
-        if gaps is None and not _ZERO_FULL_GRAD:
+        g = self._acquire(u.total)
+        gaps = getattr(u, "_grad_gaps", None)
+        if gaps is None:
             gaps, end = [], 0
             for o, n in sorted(zip(u.offsets, u.numels)):
                 if o > end:

@@ -794,7 +794,9 @@ def test_lora_fp32_adapters_take_the_gemm_path():
 @pytest.mark.parametrize("M,K,R,p,offset,strided", [
     (256, 256, 32, 0.0, 0, False), (200, 512, 64, 0.1, 0, False), (77, 1024, 192, 0.1, 8, True),
     (1024, 4096, 128, 0.1, 0, False), (33, 128, 256, 0.5, 4, False), (6144, 14336, 64, 0.1, 0, True),
-    (300, 4096, 192, 0.0, 0, True), (130, 256, 64, 0.1, 4, False)])
+    (300, 4096, 192, 0.0, 0, True), (130, 256, 64, 0.1, 4, False),
+    # R = 96 / 160 / 224: the register-staged kernel at 3, 5 and 7 32-row blocks, K split in fp32 partials
+    (77, 256, 96, 0.1, 4, True), (130, 384, 160, 0.1, 0, False), (33, 256, 224, 0.0, 0, True)])
 def test_lora_down_kernel(M, K, R, p, offset, strided):
     """lora.hip lora_down: h = drop(x) A^T (mask = the host hash, ops/_ref.py) and the x_d side output."""
     from gke_ray_train_amd.ops import _ref
@@ -833,6 +835,31 @@ def test_lora_dx_kernel(M, K, R, p, offset, acc):
     ref = (g.float() @ a.float()) * keep / (1 - p) + (dx0 if acc else 0)
     _close(dx, ref, 2e-2, 2e-2, "lora_dx")
     assert not C.lora_dx(g, a.t().contiguous()[:64].contiguous(), dx[:, :64].contiguous(), p, seed, offset, acc)
+
+
+@pytest.mark.parametrize("rows,cols", [(64, 64), (128, 192)])
+def test_transpose_64_column_tiles(rows, cols):
+    """cols % 128 == 64: the 64 x 64 tile kernel."""
+    C = _C()
+    w = torch.randn(rows, cols, device=DEV, dtype=torch.bfloat16)
+    wt = torch.empty(cols, rows, device=DEV, dtype=torch.bfloat16)
+    C.transpose_into(w, wt)
+    assert torch.equal(wt, w.t())
+
+
+@pytest.mark.parametrize("dt,blocksize", [(torch.bfloat16, 128), (torch.float32, 64)])
+def test_nf4_dequant_constant_table_kernel(dt, blocksize):
+    """Flat dequantisation on the __constant__-table kernel: a blocksize other than 64, and fp32 output."""
+    from gke_ray_train_amd import ops
+    from gke_ray_train_amd.ops import _ref
+    torch.manual_seed(13)
+    n = blocksize * 40
+    w = torch.randn(n, device=DEV, dtype=torch.bfloat16)
+    q, a = ops.nf4_quantize(w, blocksize)
+    wd = ops.nf4_dequantize(q, a, n, blocksize, dt)
+    assert wd.dtype == dt and wd.shape == (n,)
+    wr = _ref.nf4_dequantize(q.cpu(), a.cpu(), n, blocksize, dt)
+    _close(wd.cpu(), wr, 1e-2, 1e-2, "nf4 dequant")
 
 
 def test_transpose_and_nf4_dequant_t():
@@ -1421,7 +1448,7 @@ def test_attn_bwd_writes_transposed_dqkv(B, S, hq, hkv, rope, form, varlen):
 @pytest.mark.parametrize("dt,n", [(torch.bfloat16, 40_000_013), (torch.bfloat16, 3 * 1024 * 256 * 8 + 5),
                                   (torch.float32, 9_000_011)])
 def test_sumsq_unrolled_matches_float64(dt, n):
-    """Grad-norm partial sums over sizes that run the 4-load unrolled loop on every lane, on some
+    """Grad-norm partial sums over sizes that run the 2-load unrolled loop on every lane, on some
     lanes only (3 grid strides + a tail) and through the scalar remainder."""
     from gke_ray_train_amd import _native
     K = _native.kernels()

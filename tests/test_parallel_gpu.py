@@ -104,8 +104,8 @@ def test_overlapped_optimizer_matches_serial(transpose, monkeypatch):
         opt = FusedAdamW(ddp.optimizer_param_groups(0.01), lr=1e-3)
         if overlap:
             opt = OverlappedOptimizer(ddp, opt)
-            # embed, layers (GRT_OVERLAP_FINE=1: per layer its norms + 4 projections), final norm, head
-            per = 5 if os.environ.get("GRT_OVERLAP_FINE", "0") == "1" else 1
+            # embed, layers, final norm, head
+            per = 1
             assert len(opt.chunks) == per * m.config.num_hidden_layers + 3
             assert bool(opt._wt) == (transpose == "1")
         g = torch.Generator(device="cuda").manual_seed(9)

@@ -3,8 +3,7 @@
 one packed step of T tokens): per module the grouped g = s dY B products (lora_g_group), the grouped
 dB = dY^T h' token reductions (lora_tred_group), dA^T = x_d^T g (lora_tred, transposed) and the
 dropout + down-projection h' = s drop(x) A^T (lora_down). Median of --reps launches per shape, with
-the bytes of the big operand over time. Launch-time switches (GRT_LORA_G_NS, GRT_LORA_TRED_WPC, ...)
-are read once per process: A/B them with separate runs.
+the bytes of the big operand over time.
 
     python tools/lora_kernel_bench.py [--tokens 6144] [--reps 20] [--tag name]
 """
