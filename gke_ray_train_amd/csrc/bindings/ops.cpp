@@ -688,7 +688,7 @@ void check_bshd(const Tensor& t, const char* name) {
   TORCH_CHECK(t.dim() == 4, name, " must be [B, S, H, D]");
   TORCH_CHECK(t.stride(3) == 1, name, ": head_dim must be contiguous");
   if (t.scalar_type() == at::kBFloat16) {
-    TORCH_CHECK(t.size(3) == 128, name, ": bf16 kernels need head_dim 128");
+    TORCH_CHECK(grt::attn_bf16_supported((int)t.size(3)), name, ": bf16 kernels need head_dim 64 or 128");
   } else {
     TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be bf16 or fp32");
     TORCH_CHECK(grt::attn_f32_supported((int)t.size(3)), name, ": fp32 kernels need head_dim 64 or 128");
@@ -739,7 +739,8 @@ grt::AttnParams make_params(const Tensor& q, const Tensor& k, const Tensor& v, c
     check_contig(*cu_seqlens, "cu_seqlens");
     TORCH_CHECK(cu_seqlens->scalar_type() == at::kInt && cu_seqlens->is_cuda() && nseq >= 1,
                 "cu_seqlens must be int32 [num_seqs + 1] on the device");
-    TORCH_CHECK(q.scalar_type() == at::kBFloat16, "packed (cu_seqlens) attention: bf16 kernels");
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.size(3) == 128,
+                "packed (cu_seqlens) attention: bf16 kernels, head_dim 128");
     TORCH_CHECK(q.size(0) == 1 && k.size(1) == q.size(1), "packed attention: q / k / v are [1, T, H, D]");
     TORCH_CHECK(causal && !seqlens_k.has_value(), "packed attention is causal self-attention without seqlens_k");
     TORCH_CHECK(max_seqlen >= 1 && max_seqlen <= q.size(1), "max_seqlen must be in [1, T]");
@@ -783,6 +784,7 @@ std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, 
     p.ot_ld = o_t->size(1);
   }
   if (q.scalar_type() == at::kFloat) grt::attn_fwd_f32(p, cur_stream(q));
+  else if (p.D == 64) grt::attn_fwd_d64(p, cur_stream(q));
   else grt::attn_fwd(p, cur_stream(q));
   return {o, lse};
 }
@@ -842,6 +844,7 @@ std::vector<Tensor> attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& 
     bp.t_row_v = (p.Hq + p.Hkv) * p.D;
   }
   if (q.scalar_type() == at::kFloat) grt::attn_bwd_f32(bp, cur_stream(q));
+  else if (p.D == 64) grt::attn_bwd_d64(bp, cur_stream(q));
   else grt::attn_bwd(bp, cur_stream(q));
   return {dq, dk, dv};
 }
@@ -852,6 +855,7 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const opti
   check_bshd(v, "v");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16,
               "attn_decode: bf16");
+  TORCH_CHECK(q.size(3) == 128 && k.size(3) == 128 && v.size(3) == 128, "attn_decode: head_dim 128");
   TORCH_CHECK(q.size(1) == 1, "attn_decode: one query token per sequence");
   TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0), "attn_decode: k/v shapes");
   const int64_t Hq = q.size(2), Hkv = k.size(2);

@@ -241,6 +241,12 @@ void attn_decode(const AttnDecodeParams& p, hipStream_t s);
 bool attn_f32_supported(int head_dim);
 void attn_fwd_f32(const AttnParams& p, hipStream_t s);
 void attn_bwd_f32(const AttnBwdParams& p, hipStream_t s);
+// bf16 head_dim 64 (attention_d64.hip): same params and contract as attn_fwd / attn_bwd without
+// cu_seqlens, o_t, rope_cos / rope_sin and dqkv_t (those stay head_dim 128); workspace of
+// attn_bwd_workspace_floats(). attn_bf16_supported: head_dim 64 or 128 (128 = attention.hip).
+bool attn_bf16_supported(int head_dim);
+void attn_fwd_d64(const AttnParams& p, hipStream_t s);
+void attn_bwd_d64(const AttnBwdParams& p, hipStream_t s);
 
 // ---------------- 4-bit NormalFloat (nf4.hip) ----------------
 void nf4_quantize(DType dt, const void* w, uint8_t* q, float* absmax, int64_t n, int blocksize,

@@ -83,7 +83,8 @@ class _MHA(nn.Module):
         q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
         p = self.dropout if training else 0.0
         # on MI355X: the flash kernels with in-kernel probability dropout — exact fp32
-        # (attention_f32.hip, the reference's fp32 training) or bf16 (attention.hip); CPU: the
+        # (attention_f32.hip, the reference's fp32 training) or bf16 (attention.hip at head_dim 128,
+        # attention_d64.hip at 64, e.g. gpt2-small's 768 / 12); CPU: the
         # explicit fp32 math path with the same dropout mask (reference semantics, :82-86)
         o = ops.flash_attention(q, k, v, causal=True, dropout_p=p)
         return self.out_proj(o.reshape(B * S, d))

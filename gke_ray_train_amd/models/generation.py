@@ -291,7 +291,11 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              eos_token_id: Optional[Union[int, List[int]]] = None, do_sample: bool = False, temperature: float = 1.0,
              top_p: Optional[float] = None, attention_mask=None, pad_token_id=None, generator=None,
              use_graph: Optional[bool] = None, sync_every: int = 16, **_):
-    """Returns [B, prompt + generated] token ids (HF ``generate`` output convention)."""
+    """Returns [B, prompt + generated] token ids (HF ``generate`` output convention).
+
+    The HIP-graph decoder (fused RoPE epilogue, split-K decode attention) is for bf16 models with
+    head_dim 128. A head_dim-64 model (``llama3.2-1b``) generates on the eager path: its one-token
+    attention over the cache runs on the head_dim-64 flash forward kernel with ``seqlens_k``."""
     was = model.training
     model.eval()
     B, S = input_ids.shape

@@ -98,7 +98,17 @@ CONFIGS = {
     "llama3-70b": dict(vocab_size=128256, hidden_size=8192, intermediate_size=28672, num_hidden_layers=80,
                        num_attention_heads=64, num_key_value_heads=8, max_position_embeddings=8192,
                        rope_theta=500000.0, bos_token_id=128000, eos_token_id=128001, name="llama3-70b"),
-    # small configs for tests / smoke (head_dim 128 so the HIP attention path is exercised)
+    "llama3.2-1b": dict(vocab_size=128256, hidden_size=2048, intermediate_size=8192, num_hidden_layers=16,
+                        num_attention_heads=32, num_key_value_heads=8, max_position_embeddings=131072,
+                        rope_theta=500000.0, bos_token_id=128000, eos_token_id=128001, tie_word_embeddings=True,
+                        rope_scaling=dict(type="llama3", factor=32.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                                          original_max_position_embeddings=8192), name="llama3.2-1b"),
+    # small configs for tests / smoke. bf16 attention runs on HIP kernels at head_dim 128 (the fused
+    # RoPE + attention path with its packed / transposed-output / graph-decode features) and at
+    # head_dim 64 (torch RoPE, then the plain flash kernels): llama-tiny-d64 covers the latter.
+    "llama-tiny-d64": dict(vocab_size=512, hidden_size=256, intermediate_size=688, num_hidden_layers=2,
+                           num_attention_heads=4, num_key_value_heads=2, max_position_embeddings=512,
+                           name="llama-tiny-d64"),
     "llama-tiny": dict(vocab_size=512, hidden_size=256, intermediate_size=688, num_hidden_layers=2,
                        num_attention_heads=2, num_key_value_heads=2, max_position_embeddings=512, name="llama-tiny"),
     "llama-tiny-gqa": dict(vocab_size=512, hidden_size=512, intermediate_size=1376, num_hidden_layers=2,
@@ -111,6 +121,7 @@ CONFIGS["meta-llama/Llama-2-7b-hf"] = CONFIGS["llama2-7b"]
 CONFIGS["meta-llama/Meta-Llama-3.1-8B-Instruct"] = CONFIGS["llama3.1-8b"]
 CONFIGS["meta-llama/Meta-Llama-3-8B"] = CONFIGS["llama3-8b"]
 CONFIGS["meta-llama/Meta-Llama-3-70B"] = CONFIGS["llama3-70b"]
+CONFIGS["meta-llama/Llama-3.2-1B"] = CONFIGS["llama3.2-1b"]
 
 
 def get_config(name: str, **overrides) -> LlamaConfig:

@@ -276,8 +276,7 @@ def flash_attention(q, k, v, causal=True, scale=None, seqlens_k=None, dropout_p=
         # one query token per sequence (decode): split-K kernel over the cached keys; every cached
         # key is at or before the query position, so the causal mask is the valid-length mask
         return _native.kernels().attn_decode(q, k, v, seqlens_k, scale)
-    if _gpu(q) and ((q.dtype == torch.bfloat16 and q.shape[-1] == 128) or
-                    (q.dtype == torch.float32 and q.shape[-1] in (64, 128))):
+    if _gpu(q) and q.dtype in (torch.bfloat16, torch.float32) and q.shape[-1] in (64, 128):
         return _FlashAttn.apply(q, k, v, causal, scale, seqlens_k, float(dropout_p), seed)
     if _gpu(q):
         _warn_once(f"flash_attention: no gfx950 kernel for dtype={q.dtype} head_dim={q.shape[-1]}; "

@@ -5,6 +5,13 @@ the fp32 math reference (max abs error of O and of dQ / dK / dV). TFLOP/s count 
 causal FLOPs: 2 matmuls forward, 5 backward. The kernel generations compared in round 2
 (profiles/r2_attention.md) were selected through a since-removed variant switch.
 usage: python tools/attn_ab.py [--rounds 7]
+
+--head-dim 64: the head_dim-64 bf16 kernels (attention_d64.hip) against the path they replaced,
+the fp32 math attention (ops/_ref.attention and its autograd backward on the same GPU tensors), at
+the two 64-wide training shapes: the gpt2-small BasicLLM step (B16 S256 H12 causal, dropout 0.1)
+and the Llama-3.2-1B step (B8 S1024 Hq32 Hkv8 causal). Forward and forward + backward, interleaved
+rounds after a warm-up, device events; median, min and max per variant, and for information the
+D = 128 kernels at the same B, S, H.
 """
 import argparse
 import json
@@ -93,12 +100,80 @@ def run(shape, rounds, iters):
         print(json.dumps({"shape": f"B{B} S{S} Hq{Hq} Hkv{Hkv} D128 causal", "kernel": name, **r}), flush=True)
 
 
+def run_d64(shape, dropout_p, rounds, iters):
+    B, S, Hq, Hkv = shape
+    g = torch.Generator(device="cuda").manual_seed(0)
+
+    def mk(D):
+        return [torch.randn(B, S, h, D, device="cuda", dtype=torch.bfloat16, generator=g) for h in (Hq, Hkv, Hkv, Hq)]
+    q, k, v, do = mk(64)
+    q2, k2, v2, do2 = mk(128)
+    qr, kr, vr = (t.detach().clone().requires_grad_() for t in (q, k, v))
+    seed = 1234
+
+    def kern_fwd(q=q, k=k, v=v, D=64):
+        return C.attn_fwd(q, k, v, None, D ** -0.5, True, None, dropout_p, seed)
+
+    def kern_fb(q=q, k=k, v=v, do=do, D=64):
+        o, lse = C.attn_fwd(q, k, v, None, D ** -0.5, True, None, dropout_p, seed)
+        return C.attn_bwd(do, q, k, v, o, lse, None, None, None, D ** -0.5, True, None, dropout_p, seed)
+
+    def ref_fwd():
+        return _ref.attention(qr, kr, vr, causal=True, dropout_p=dropout_p, seed=seed)
+
+    def ref_fb():
+        for t in (qr, kr, vr):
+            t.grad = None
+        ref_fwd().backward(do)
+
+    variants = {
+        "d64_fwd": kern_fwd, "d64_fwd_bwd": kern_fb, "math_fwd": ref_fwd, "math_fwd_bwd": ref_fb,
+        "d128_fwd": lambda: kern_fwd(q2, k2, v2, 128), "d128_fwd_bwd": lambda: kern_fb(q2, k2, v2, do2, 128),
+    }
+    # agreement of the two timed paths before timing them
+    o, _ = kern_fwd()
+    dq, dk, dv = kern_fb()
+    ref_fb()
+    err = {"o": (o.float() - ref_fwd().detach().float()).abs().max().item(),
+           "dq": (dq.float() - qr.grad.float()).abs().max().item(),
+           "dk": (dk.float() - kr.grad.float()).abs().max().item(),
+           "dv": (dv.float() - vr.grad.float()).abs().max().item()}
+    for fn in variants.values():  # warm-up
+        ev_time(fn, 2)
+    ts = {n: [] for n in variants}
+    for _ in range(rounds):
+        for n, fn in variants.items():
+            ts[n].append(ev_time(fn, iters))
+    name = f"B{B} S{S} Hq{Hq} Hkv{Hkv} causal dropout {dropout_p}"
+    print(json.dumps({"shape": name, "max_abs_err_vs_math": err}), flush=True)
+    flop_mm = 2 * B * Hq * S * S / 2  # one causal matmul, per unit of head_dim
+    st = {}
+    for n, t in ts.items():
+        D = 128 if n.startswith("d128") else 64
+        nmm = 2 if n.endswith("_fwd") else 7
+        st[n] = dict(us=round(statistics.median(t), 1), min=round(min(t), 1), max=round(max(t), 1),
+                     tflops=round(nmm * flop_mm * D / statistics.median(t) / 1e6, 1))
+        print(json.dumps({"shape": name, "variant": n, **st[n]}), flush=True)
+    for part in ("fwd", "fwd_bwd"):
+        a, b = st[f"d64_{part}"], st[f"math_{part}"]
+        spread = (a["max"] - a["min"]) + (b["max"] - b["min"])
+        print(json.dumps({"shape": name, "part": part, "speedup": round(b["us"] / a["us"], 2),
+                          "gain_us": round(b["us"] - a["us"], 1), "spread_us": round(spread, 1),
+                          "faster_beyond_spread": b["us"] - a["us"] > spread}), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--scheds", default="", help="comma-separated workgroup schedules to A/B (attn_set_schedule)")
+    ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128),
+                    help="64: the head_dim-64 kernels against the fp32 math path they replaced")
     a = ap.parse_args()
     SCHEDS = a.scheds
+    if a.head_dim == 64:
+        run_d64((16, 256, 12, 12), 0.1, a.rounds, a.iters)
+        run_d64((8, 1024, 32, 8), 0.0, a.rounds, a.iters)
+        sys.exit(0)
     for shape in ((8, 1024, 32, 32), (2, 2048, 32, 8)):
         run(shape, a.rounds, a.iters)
