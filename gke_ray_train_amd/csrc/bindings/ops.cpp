@@ -849,6 +849,98 @@ std::vector<Tensor> attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& 
   return {dq, dk, dv};
 }
 
+// ---- RoPE + attention on the fused QKV buffer, bf16 head_dim 64 (rope_attention_d64.hip) ----
+// row stride of t seen as T token rows of Hq heads: [T, Hq * 64] or [T, Hq, 64] with unit last stride and
+// heads 64 apart; the rows may be the head of a wider row buffer
+int64_t d64_row_stride(const Tensor& t, int64_t T, int64_t hq, const char* op, const char* name) {
+  check_cuda(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, op, ": ", name, " must be bf16");
+  const bool ok = t.dim() == 2 ? t.size(0) == T && t.size(1) == hq * 64 && t.stride(1) == 1
+                               : t.dim() == 3 && t.size(0) == T && t.size(1) == hq && t.size(2) == 64 &&
+                                     t.stride(2) == 1 && (hq == 1 || t.stride(1) == 64);
+  const int64_t ld = ok && T > 1 ? t.stride(0) : hq * 64;  // one row: its stride is never used
+  TORCH_CHECK(ok && ld >= hq * 64, op, ": ", name, " must be [T, Hq * 64] or [T, Hq, 64] token rows (unit last stride, "
+              "heads 64 apart, row stride >= Hq * 64)");
+  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name, " alignment");
+  return ld;
+}
+
+grt::RopeAttnD64Params rope_attn_d64_params(const char* op, const Tensor& qkv, const Tensor& cos, const Tensor& sin,
+                                            const Tensor& o, int64_t B, int64_t S, int64_t hq, int64_t hkv,
+                                            double scale, bool causal, const optional<Tensor>& cu_seqlens,
+                                            int64_t max_seqlen) {
+  check_cuda(qkv, "qkv");
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, op, ": qkv must be bf16, got ", qkv.scalar_type());
+  TORCH_CHECK(qkv.dim() == 2 && qkv.is_contiguous(), op, ": qkv must be a contiguous [T, (Hq + 2 Hkv) * 64]");
+  TORCH_CHECK(hq >= 1 && hkv >= 1 && hq % hkv == 0, op, ": Hq must be a multiple of Hkv");
+  TORCH_CHECK(qkv.size(1) == (hq + 2 * hkv) * 64, op, ": qkv width ", qkv.size(1), " is not (Hq + 2 Hkv) * 64 = ",
+              (hq + 2 * hkv) * 64);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, op, ": qkv alignment");
+  const int64_t T = qkv.size(0);
+  TORCH_CHECK(B >= 1 && S >= 1 && B * S == T, op, ": B * S must equal the token rows of qkv");
+  const bool packed = cu_seqlens.has_value();
+  const int64_t rows = packed ? max_seqlen : S;  // longest sequence = positions the tables must cover
+  int64_t nseq = B;
+  if (packed) {
+    TORCH_CHECK(cu_seqlens->is_cuda() && cu_seqlens->scalar_type() == at::kInt && cu_seqlens->is_contiguous() &&
+                    cu_seqlens->dim() == 1 && cu_seqlens->numel() >= 2,
+                op, ": cu_seqlens must be int32 [num_seqs + 1] on the device");
+    TORCH_CHECK(max_seqlen >= 1 && max_seqlen <= T, op, ": max_seqlen must be in [1, T]");
+    nseq = cu_seqlens->numel() - 1;
+  }
+  check_contig(cos, "cos");
+  check_contig(sin, "sin");
+  TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat, op, ": cos/sin must be fp32");
+  TORCH_CHECK(cos.dim() == 2 && cos.size(1) == 32 && sin.sizes() == cos.sizes(), op, ": cos/sin must be [rows, 32]");
+  TORCH_CHECK(cos.size(0) >= rows, op, ": cos/sin tables have ", cos.size(0), " rows, the longest sequence has ", rows);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(cos.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(sin.data_ptr()) % 16 == 0,
+              op, ": cos/sin alignment");
+  TORCH_CHECK(nseq * hq * rows < INT_MAX / 64 && T < INT_MAX, op, ": problem too large");
+  grt::RopeAttnD64Params p{};
+  p.qkv = qkv.data_ptr(); p.ld = qkv.size(1);
+  p.cos = cos.data_ptr<float>(); p.sin = sin.data_ptr<float>();
+  p.o = o.data_ptr(); p.o_ld = d64_row_stride(o, T, hq, op, "o");
+  p.cu_seqlens = packed ? cu_seqlens->data_ptr<int32_t>() : nullptr;
+  p.T = T; p.nseq = (int)nseq; p.S = (int)rows; p.Hq = (int)hq; p.Hkv = (int)hkv;
+  p.scale = (float)scale; p.causal = causal ? 1 : 0;
+  return p;
+}
+
+// o: [T, Hq, 64] token rows to write (may be the head of wider rows); returns lse fp32 [nseq, Hq, S]
+Tensor rope_attn_fwd_d64(const Tensor& qkv, const Tensor& cos, const Tensor& sin, Tensor& o, int64_t B, int64_t S,
+                         int64_t hq, int64_t hkv, double scale, bool causal, const optional<Tensor>& cu_seqlens,
+                         int64_t max_seqlen) {
+  auto p = rope_attn_d64_params("rope_attn_fwd_d64", qkv, cos, sin, o, B, S, hq, hkv, scale, causal, cu_seqlens,
+                                max_seqlen);
+  c10::OptionalDeviceGuard g(qkv.device());
+  auto lse = at::empty({(int64_t)p.nseq, hq, (int64_t)p.S}, qkv.options().dtype(at::kFloat));
+  p.lse = lse.data_ptr<float>();
+  grt::rope_attn_fwd_d64(p, cur_stream(qkv));
+  return lse;
+}
+
+// writes every element of dqkv [T, (Hq + 2 Hkv) * 64]: un-rotated dQ / dK and dV in their columns
+void rope_attn_bwd_d64(const Tensor& dout, const Tensor& qkv, const Tensor& cos, const Tensor& sin, const Tensor& o,
+                       const Tensor& lse, Tensor& dqkv, int64_t B, int64_t S, int64_t hq, int64_t hkv, double scale,
+                       bool causal, const optional<Tensor>& cu_seqlens, int64_t max_seqlen) {
+  const char* op = "rope_attn_bwd_d64";
+  auto p = rope_attn_d64_params(op, qkv, cos, sin, o, B, S, hq, hkv, scale, causal, cu_seqlens, max_seqlen);
+  c10::OptionalDeviceGuard g(qkv.device());
+  check_cuda(lse, "lse");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == (int64_t)p.nseq * hq * p.S,
+              op, ": lse must be fp32 [B, Hq, S] ([num_seqs, Hq, max_seqlen] when packed)");
+  check_cuda(dqkv, "dqkv");
+  TORCH_CHECK(dqkv.scalar_type() == at::kBFloat16 && dqkv.is_contiguous() && dqkv.sizes() == qkv.sizes() &&
+                  reinterpret_cast<uintptr_t>(dqkv.data_ptr()) % 16 == 0,
+              op, ": dqkv must be a contiguous bf16 tensor of qkv's shape");
+  p.lse = const_cast<float*>(lse.data_ptr<float>());
+  p.dout = dout.data_ptr(); p.do_ld = d64_row_stride(dout, p.T, hq, op, "do");
+  p.dqkv = dqkv.data_ptr();
+  auto ws = at::empty({(int64_t)p.nseq * hq * p.S}, qkv.options().dtype(at::kFloat));
+  p.delta = ws.data_ptr<float>();
+  grt::rope_attn_bwd_d64(p, cur_stream(qkv));
+}
+
 Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& seqlens_k, double scale) {
   check_bshd(q, "q");
   check_bshd(k, "k");
@@ -1387,6 +1479,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seqlens_k"), py::arg("dropout_p") = 0.0, py::arg("seed") = 0, py::arg("rope_cos") = py::none(),
         py::arg("rope_sin") = py::none(), py::arg("cu_seqlens") = py::none(), py::arg("max_seqlen") = 0,
         py::arg("dqkv_t") = py::none());
+  m.def("rope_attn_fwd_d64", &rope_attn_fwd_d64, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("o"),
+        py::arg("B"), py::arg("S"), py::arg("hq"), py::arg("hkv"), py::arg("scale"), py::arg("causal"),
+        py::arg("cu_seqlens") = py::none(), py::arg("max_seqlen") = 0,
+        "bf16 head_dim 64: RoPE + flash attention straight from the fused QKV rows (packed with cu_seqlens) -> lse");
+  m.def("rope_attn_bwd_d64", &rope_attn_bwd_d64, py::arg("do"), py::arg("qkv"), py::arg("cos"), py::arg("sin"),
+        py::arg("o"), py::arg("lse"), py::arg("dqkv"), py::arg("B"), py::arg("S"), py::arg("hq"), py::arg("hkv"),
+        py::arg("scale"), py::arg("causal"), py::arg("cu_seqlens") = py::none(), py::arg("max_seqlen") = 0,
+        "backward of rope_attn_fwd_d64: un-rotated dQ / dK and dV into the columns of dqkv (every element written)");
   m.def("attn_set_schedule", &grt::attn_set_schedule,
         "bf16 attention causal-pair / XCD-grouped schedule, bit mask: 1 = forward, 2 = dQ, 4 = dK/dV");
   m.def("attn_get_schedule", &grt::attn_get_schedule);

@@ -247,6 +247,28 @@ void attn_bwd_f32(const AttnBwdParams& p, hipStream_t s);
 bool attn_bf16_supported(int head_dim);
 void attn_fwd_d64(const AttnParams& p, hipStream_t s);
 void attn_bwd_d64(const AttnBwdParams& p, hipStream_t s);
+// bf16 head_dim 64 on the fused QKV buffer (rope_attention_d64.hip): RoPE (rotate-half, position =
+// row index inside its own sequence) is applied in fp32 where a Q / K row or tile is loaded, and
+// undone on the fp32 dQ / dK accumulators before they are stored, so no rotated copy of q / k and
+// no separate dq / dk exist. Sequence b is token rows [cu[b], cu[b+1]) when cu_seqlens is given
+// (S = the longest sequence), rows [b S, (b + 1) S) otherwise. lse / delta are [nseq, Hq, S].
+struct RopeAttnD64Params {
+  const void* qkv; int64_t ld;          // [T, (Hq + 2 Hkv) * 64], row stride ld
+  const float* cos; const float* sin;   // fp32 [>= S, 32]
+  void* o; int64_t o_ld;                // [T, Hq, 64] rows of stride o_ld (>= Hq * 64; the tail is not written)
+  float* lse;
+  const int32_t* cu_seqlens;            // int32 [nseq + 1] or null
+  int64_t T;                            // token rows of qkv / o / dout / dqkv
+  int nseq, S, Hq, Hkv;
+  float scale;
+  int causal;
+  // backward only
+  const void* dout; int64_t do_ld;      // [T, Hq, 64] rows of stride do_ld
+  void* dqkv;                           // [T, (Hq + 2 Hkv) * 64], row stride ld; every element written
+  float* delta;                         // fp32 workspace [nseq, Hq, S]
+};
+void rope_attn_fwd_d64(const RopeAttnD64Params& p, hipStream_t s);
+void rope_attn_bwd_d64(const RopeAttnD64Params& p, hipStream_t s);
 
 // ---------------- 4-bit NormalFloat (nf4.hip) ----------------
 void nf4_quantize(DType dt, const void* w, uint8_t* q, float* absmax, int64_t n, int blocksize,

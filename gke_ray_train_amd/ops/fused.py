@@ -401,13 +401,54 @@ class _RopeAttention(torch.autograd.Function):
         return dqkv, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
+# bf16 head_dim 64: RoPE inside the attention kernels, straight from / into the fused QKV rows, one
+# launch set for all packed sequences (rope_attention_d64.hip); GRT_ROPE_ATTN_D64=0 -> torch RoPE,
+# then the plain flash kernels (sequence by sequence when packed)
+_ROPE_ATTN_D64 = os.environ.get("GRT_ROPE_ATTN_D64", "1") != "0"
+
+
+class _RopeAttentionD64(torch.autograd.Function):
+    """``_RopeAttention`` for head_dim 64: qkv [B*S, (Hq + 2 Hkv) * 64] -> o [B*S, Hq * 64]. The kernels
+    rotate q / k as they load them and un-rotate dQ / dK as they store them into dqkv's columns, so
+    only qkv, o, lse and the tables are saved and no dq / dk / rotated copy exists."""
+
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, B, S, hq, hkv, causal, scale, varlen=None, pad=0):
+        C = _native.kernels()
+        qkv = qkv.contiguous()
+        cu, ml = (varlen.cu, varlen.max_len) if varlen is not None else (None, 0)
+        # the output rows may be the head of [o | LoRA h] row buffers (the o_proj's K-concat tail)
+        ld = hq * 64 + pad
+        ow = torch.empty(B * S, ld, device=qkv.device, dtype=qkv.dtype)
+        o = ow.as_strided((B * S, hq, 64), (ld, 64, 1))
+        lse = C.rope_attn_fwd_d64(qkv, cos, sin, o, B, S, hq, hkv, scale, causal, cu_seqlens=cu, max_seqlen=ml)
+        ctx.save_for_backward(qkv, o, lse, cos, sin)
+        ctx.dims = (B, S, hq, hkv, causal, scale)
+        ctx.varlen = varlen
+        return ow[:, :hq * 64]
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse, cos, sin = ctx.saved_tensors
+        B, S, hq, hkv, causal, scale = ctx.dims
+        vl = ctx.varlen
+        cu, ml = (vl.cu, vl.max_len) if vl is not None else (None, 0)
+        dqkv = torch.empty_like(qkv)
+        _native.kernels().rope_attn_bwd_d64(do.contiguous(), qkv, cos, sin, o, lse, dqkv, B, S, hq, hkv, scale,
+                                            causal, cu_seqlens=cu, max_seqlen=ml)
+        return dqkv, None, None, None, None, None, None, None, None, None, None
+
+
 def rope_attention(qkv, cos, sin, B, S, hq, hkv, D, causal=True, scale=None, varlen: "Varlen" = None,
                    pad: int = 0, bwd_t: bool = False, fwd_t: bool = False):
     """``varlen``: the B*S rows are padding-free packed sequences (B = 1; see ``Varlen``).
     ``pad`` as in ``rms_norm``: the o_proj's LoRA tail after each output row. ``bwd_t``: the
     backward also writes dqkv^T for a trainable QKV projection's weight gradient, ``fwd_t``: the
-    forward also writes o^T for a trainable o projection's (GRT_ATTN_DQKV_T=0: neither)."""
+    forward also writes o^T for a trainable o projection's (GRT_ATTN_DQKV_T=0: neither; ignored at
+    head_dim 64, where the projections transpose by themselves)."""
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if _gpu(qkv) and qkv.dtype == torch.bfloat16 and D == 64 and _ROPE_ATTN_D64:
+        return _tail(_RopeAttentionD64.apply(qkv, cos, sin, B, S, hq, hkv, causal, scale, varlen, pad), pad)
     if _gpu(qkv) and qkv.dtype == torch.bfloat16 and D == 128:
         bwd_t = bwd_t and _ATTN_DQKV_T
         fwd_t = fwd_t and _ATTN_DQKV_T and not pad

@@ -12,6 +12,11 @@ the two 64-wide training shapes: the gpt2-small BasicLLM step (B16 S256 H12 caus
 and the Llama-3.2-1B step (B8 S1024 Hq32 Hkv8 causal). Forward and forward + backward, interleaved
 rounds after a warm-up, device events; median, min and max per variant, and for information the
 D = 128 kernels at the same B, S, H.
+
+--head-dim 64 --rope [--packed L1,L2,...]: ``ops.rope_attention`` at Hq32 Hkv8 on the qkv-native
+kernels (rope_attention_d64.hip) against the path they replace (GRT_ROPE_ATTN_D64=0 semantics: torch
+RoPE, then the flash kernels, one call per sequence when packed), unpacked B8 S1024 or the packed
+lengths; same protocol, both arms checked against the fp32 math path first.
 """
 import argparse
 import json
@@ -162,6 +167,71 @@ def run_d64(shape, dropout_p, rounds, iters):
                           "faster_beyond_spread": b["us"] - a["us"] > spread}), flush=True)
 
 
+def run_rope_d64(B, S, lens, rounds, iters, Hq=32, Hkv=8):
+    """``ops.rope_attention`` at head_dim 64, qkv-native kernels (rope_attention_d64.hip) against the
+    path they replace (GRT_ROPE_ATTN_D64=0: torch RoPE, then the flash kernels, one call per
+    sequence when packed). ``lens``: packed sequence lengths, or None for B sequences of S rows."""
+    from gke_ray_train_amd import ops
+    from gke_ray_train_amd.ops import fused
+    D = 64
+    g = torch.Generator(device="cuda").manual_seed(0)
+    vl = ops.Varlen(lens, torch.device("cuda", 0)) if lens else None
+    if vl is not None:
+        B, S = 1, vl.total
+    T = B * S
+    rows = vl.max_len if vl is not None else S
+    qkv = torch.randn(T, (Hq + 2 * Hkv) * D, device="cuda", dtype=torch.bfloat16, generator=g).requires_grad_()
+    do = torch.randn(T, Hq * D, device="cuda", dtype=torch.bfloat16, generator=g)
+    cos, sin = _ref.rope_tables(rows, D, device="cuda")
+
+    def call(new, bwd):
+        fused._ROPE_ATTN_D64 = new
+        qkv.grad = None
+        o = ops.rope_attention(qkv, cos, sin, B, S, Hq, Hkv, D, causal=True, varlen=vl)
+        if bwd:
+            o.backward(do)
+        return o
+
+    variants = {"new_fwd": lambda: call(True, False), "new_fwd_bwd": lambda: call(True, True),
+                "parent_fwd": lambda: call(False, False), "parent_fwd_bwd": lambda: call(False, True)}
+    # both arms against the fp32 math path, sequence by sequence
+    x = qkv.detach().float().requires_grad_()
+    xr = x.view(T, Hq + 2 * Hkv, D)
+    pos = vl.pos if vl is not None else torch.arange(T, device="cuda") % S
+    bounds = list(zip(vl.cu_host[:-1], vl.cu_host[1:])) if vl is not None else [(b * S, (b + 1) * S) for b in range(B)]
+    qr, kr = (_ref.apply_rope(xr[:, a:b], cos, sin, pos) for a, b in ((0, Hq), (Hq, Hq + Hkv)))
+    vr = xr[:, Hq + Hkv:]
+    ref = torch.cat([_ref.attention(qr[a:b].unsqueeze(0), kr[a:b].unsqueeze(0), vr[a:b].unsqueeze(0), causal=True)[0]
+                     for a, b in bounds]).reshape(T, Hq * D)
+    ref.backward(do.float())
+    err = {}
+    for arm, new in (("new", True), ("parent", False)):
+        o = call(new, True)
+        err[arm] = {"o": (o.float() - ref.detach()).abs().max().item(),
+                    "dqkv": (qkv.grad.float() - x.grad).abs().max().item()}
+    name = (f"packed {','.join(map(str, lens))}" if lens else f"B{B} S{S}") + f" Hq{Hq} Hkv{Hkv} D64 causal rope"
+    print(json.dumps({"shape": name, "max_abs_err_vs_math": err}), flush=True)
+    del x, xr, qr, kr, vr, ref
+    for fn in variants.values():  # warm-up
+        ev_time(fn, 2)
+    ts = {n: [] for n in variants}
+    for _ in range(rounds):
+        for n, fn in variants.items():
+            ts[n].append(ev_time(fn, iters))
+    fused._ROPE_ATTN_D64 = True
+    st = {}
+    for n, t in ts.items():
+        st[n] = dict(us=round(statistics.median(t), 1), min=round(min(t), 1), max=round(max(t), 1))
+        print(json.dumps({"shape": name, "variant": n, **st[n]}), flush=True)
+    for part in ("fwd", "fwd_bwd"):
+        a, b = st[f"new_{part}"], st[f"parent_{part}"]
+        spread = (a["max"] - a["min"]) + (b["max"] - b["min"])
+        print(json.dumps({"shape": name, "part": part, "speedup": round(b["us"] / a["us"], 2),
+                          "gain_us": round(b["us"] - a["us"], 1), "spread_us": round(spread, 1),
+                          "faster_beyond_spread": b["us"] - a["us"] > spread,
+                          "slower_beyond_spread": a["us"] - b["us"] > spread}), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -169,8 +239,17 @@ if __name__ == "__main__":
     ap.add_argument("--scheds", default="", help="comma-separated workgroup schedules to A/B (attn_set_schedule)")
     ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128),
                     help="64: the head_dim-64 kernels against the fp32 math path they replaced")
+    ap.add_argument("--rope", action="store_true",
+                    help="with --head-dim 64: ops.rope_attention, qkv-native kernels against GRT_ROPE_ATTN_D64=0")
+    ap.add_argument("--packed", default="", help="with --rope: comma-separated packed sequence lengths "
+                    "(default: unpacked B8 S1024)")
     a = ap.parse_args()
     SCHEDS = a.scheds
+    if a.rope or a.packed:
+        if a.head_dim != 64 or not a.rope:
+            ap.error("--rope / --packed measure the head_dim-64 op: use --head-dim 64 --rope [--packed L1,L2,...]")
+        run_rope_d64(8, 1024, [int(x) for x in a.packed.split(",")] if a.packed else None, a.rounds, a.iters)
+        sys.exit(0)
     if a.head_dim == 64:
         run_d64((16, 256, 12, 12), 0.1, a.rounds, a.iters)
         run_d64((8, 1024, 32, 8), 0.0, a.rounds, a.iters)
