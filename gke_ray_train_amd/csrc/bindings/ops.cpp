@@ -44,25 +44,56 @@ void check_vec(const Tensor& t, int64_t d, const char* name) {
 const void* ptr_or_null(const optional<Tensor>& t) { return t.has_value() ? t->data_ptr() : nullptr; }
 
 // ------------------------------------------------------------------ norms
+// The norm kernels index every operand from the row tensor's shape alone, so each binding checks
+// every operand against it first: rows [rows, d] (x / h; residual, dy, dres like it), per-feature
+// vectors [d] (w, b) and per-row fp32 statistics [rows] (mean, rstd).
+
+// the row tensor: bf16 / fp32, contiguous, 16-byte rows, no wider than the dispatch ladders of
+// norm.hip cover (a wider row would lose its tail silently); returns d
+int64_t check_norm_rows(const Tensor& t, const char* name) {
+  check_contig(t, name);
+  dtype_of(t);
+  TORCH_CHECK(t.dim() >= 1 && t.size(-1) > 0, name, " must be [..., d] with d > 0");
+  const int64_t d = t.size(-1);
+  check_vec(t, d, name);
+  const int64_t vec = t.scalar_type() == at::kBFloat16 ? 8 : 4;
+  TORCH_CHECK(d / vec <= grt::norm_max_chunks(), name, ": last dim ", d, " is wider than the norm kernels' limit of ",
+              grt::norm_max_chunks(), " 16-byte chunks (", grt::norm_max_chunks() * vec, " elements of ",
+              t.scalar_type(), ")");
+  return d;
+}
+void check_norm_like(const Tensor& t, const Tensor& rows_t, const char* name) {
+  check_contig(t, name);
+  TORCH_CHECK(t.sizes() == rows_t.sizes() && t.scalar_type() == rows_t.scalar_type() && t.device() == rows_t.device(),
+              name, " must match the input's shape, dtype and device");
+}
+void check_norm_param(const Tensor& t, const Tensor& rows_t, int64_t d, const char* name) {
+  check_contig(t, name);
+  TORCH_CHECK(t.numel() == d && t.scalar_type() == rows_t.scalar_type() && t.device() == rows_t.device(), name,
+              " must hold ", d, " elements in the input's dtype on its device");
+}
+void check_norm_stat(const Tensor& t, const Tensor& rows_t, int64_t rows, const char* name) {
+  check_contig(t, name);
+  TORCH_CHECK(t.numel() == rows && t.scalar_type() == at::kFloat && t.device() == rows_t.device(), name,
+              " must hold one fp32 value per row (", rows, ") on the input's device");
+}
+
 // pad > 0: y is the [rows, d] view of a [rows, d + pad] buffer (row stride d + pad) whose last pad
 // columns a consumer fills (the LoRA h of a K-concatenated projection, peft/lora.py)
 std::vector<Tensor> rmsnorm_fwd(const Tensor& x, const optional<Tensor>& residual, const Tensor& w,
                                 double eps, int64_t pad) {
-  check_contig(x, "x");
-  check_contig(w, "w");
+  const int64_t d = check_norm_rows(x, "x"), rows = x.numel() / d;
+  check_norm_param(w, x, d, "w");
   c10::OptionalDeviceGuard g(x.device());
-  const int64_t d = x.size(-1), rows = x.numel() / d;
-  check_vec(x, d, "x");
-  TORCH_CHECK(w.numel() == d && w.scalar_type() == x.scalar_type(), "weight shape/dtype mismatch");
   TORCH_CHECK(pad >= 0 && pad % 8 == 0 && (pad == 0 || x.dim() == 2), "rmsnorm_fwd: pad % 8 == 0 on [rows, d]");
   auto y = pad == 0 ? at::empty_like(x) : at::empty({rows, d + pad}, x.options()).narrow(1, 0, d);
   auto rstd = at::empty({rows}, x.options().dtype(at::kFloat));
   Tensor h;
   if (residual.has_value()) {
-    check_contig(*residual, "residual");
-    TORCH_CHECK(residual->sizes() == x.sizes() && residual->scalar_type() == x.scalar_type(), "residual mismatch");
+    check_norm_like(*residual, x, "residual");
     h = at::empty_like(x);
   }
+  if (rows == 0) return {y, residual.has_value() ? h : x, rstd};
   grt::rmsnorm_fwd(dtype_of(x), x.data_ptr(), ptr_or_null(residual), w.data_ptr(), y.data_ptr(),
                    residual.has_value() ? h.data_ptr() : nullptr, rstd.data_ptr<float>(), rows, (int)d,
                    (float)eps, cur_stream(x), d + pad);
@@ -73,20 +104,19 @@ std::vector<Tensor> rmsnorm_fwd(const Tensor& x, const optional<Tensor>& residua
 // gradient slot; accumulate adds) and the second result is dw_out itself.
 std::vector<Tensor> rmsnorm_bwd(const Tensor& dy, const Tensor& h, const Tensor& w, const Tensor& rstd,
                                 const optional<Tensor>& dres, const optional<Tensor>& dw_out, bool accumulate) {
-  check_contig(dy, "dy");
-  check_contig(h, "h");
-  c10::OptionalDeviceGuard g(dy.device());
-  const int64_t d = h.size(-1), rows = h.numel() / d;
-  TORCH_CHECK(dy.sizes() == h.sizes() && dy.scalar_type() == h.scalar_type(), "dy/h mismatch");
-  if (dres.has_value()) {
-    check_contig(*dres, "dres");
-    TORCH_CHECK(dres->sizes() == h.sizes() && dres->scalar_type() == h.scalar_type(), "dres mismatch");
-  }
-  if (dw_out.has_value()) {
-    check_contig(*dw_out, "dw_out");
-    TORCH_CHECK(dw_out->numel() == d && dw_out->scalar_type() == h.scalar_type(), "dw_out: [d] in the dtype of h");
-  }
+  const int64_t d = check_norm_rows(h, "h"), rows = h.numel() / d;
+  check_norm_like(dy, h, "dy");
+  check_norm_param(w, h, d, "w");
+  check_norm_stat(rstd, h, rows, "rstd");
+  if (dres.has_value()) check_norm_like(*dres, h, "dres");
+  if (dw_out.has_value()) check_norm_param(*dw_out, h, d, "dw_out");
+  c10::OptionalDeviceGuard g(h.device());
   auto dx = at::empty_like(h);
+  if (rows == 0) {  // nothing to sum: a zero gradient, or dw_out as it is when accumulating
+    if (!dw_out.has_value()) return {dx, at::zeros({d}, h.options().dtype(at::kFloat))};
+    if (!accumulate) dw_out->zero_();
+    return {dx, *dw_out};
+  }
   Tensor dw = dw_out.has_value() ? *dw_out : at::empty({d}, h.options().dtype(at::kFloat));
   auto ws = at::empty({grt::norm_bwd_workspace_floats(rows, (int)d)}, h.options().dtype(at::kFloat));
   grt::rmsnorm_bwd(dtype_of(h), dy.data_ptr(), h.data_ptr(), w.data_ptr(), rstd.data_ptr<float>(),
@@ -99,17 +129,14 @@ std::vector<Tensor> rmsnorm_bwd(const Tensor& dy, const Tensor& h, const Tensor&
 // dX only (frozen norm weight: LoRA / QLoRA): no weight-gradient slab, no column-sum launch
 Tensor rmsnorm_bwd_dx(const Tensor& dy, const Tensor& h, const Tensor& w, const Tensor& rstd,
                       const optional<Tensor>& dres) {
-  check_contig(dy, "dy");
-  check_contig(h, "h");
-  c10::OptionalDeviceGuard g(dy.device());
-  const int64_t d = h.size(-1), rows = h.numel() / d;
-  TORCH_CHECK(dy.sizes() == h.sizes() && dy.scalar_type() == h.scalar_type(), "dy/h mismatch");
-  TORCH_CHECK(w.numel() == d && w.scalar_type() == h.scalar_type() && rstd.numel() == rows, "w / rstd shapes");
-  if (dres.has_value()) {
-    check_contig(*dres, "dres");
-    TORCH_CHECK(dres->sizes() == h.sizes() && dres->scalar_type() == h.scalar_type(), "dres mismatch");
-  }
+  const int64_t d = check_norm_rows(h, "h"), rows = h.numel() / d;
+  check_norm_like(dy, h, "dy");
+  check_norm_param(w, h, d, "w");
+  check_norm_stat(rstd, h, rows, "rstd");
+  if (dres.has_value()) check_norm_like(*dres, h, "dres");
+  c10::OptionalDeviceGuard g(h.device());
   auto dx = at::empty_like(h);
+  if (rows == 0) return dx;
   grt::rmsnorm_bwd(dtype_of(h), dy.data_ptr(), h.data_ptr(), w.data_ptr(), rstd.data_ptr<float>(),
                    ptr_or_null(dres), dx.data_ptr(), nullptr, nullptr, rows, (int)d, cur_stream(h), nullptr, 0);
   return dx;
@@ -117,20 +144,19 @@ Tensor rmsnorm_bwd_dx(const Tensor& dy, const Tensor& h, const Tensor& w, const 
 
 std::vector<Tensor> layernorm_fwd(const Tensor& x, const optional<Tensor>& residual, const Tensor& w,
                                   const optional<Tensor>& b, double eps) {
-  check_contig(x, "x");
+  const int64_t d = check_norm_rows(x, "x"), rows = x.numel() / d;
+  check_norm_param(w, x, d, "w");
+  if (b.has_value()) check_norm_param(*b, x, d, "b");
   c10::OptionalDeviceGuard g(x.device());
-  const int64_t d = x.size(-1), rows = x.numel() / d;
-  check_vec(x, d, "x");
-  TORCH_CHECK(w.numel() == d && w.scalar_type() == x.scalar_type(), "weight shape/dtype mismatch");
   auto y = at::empty_like(x);
   auto mean = at::empty({rows}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({rows}, x.options().dtype(at::kFloat));
   Tensor h;
   if (residual.has_value()) {
-    check_contig(*residual, "residual");
-    TORCH_CHECK(residual->sizes() == x.sizes(), "residual mismatch");
+    check_norm_like(*residual, x, "residual");
     h = at::empty_like(x);
   }
+  if (rows == 0) return {y, residual.has_value() ? h : x, mean, rstd};
   grt::layernorm_fwd(dtype_of(x), x.data_ptr(), ptr_or_null(residual), w.data_ptr(), ptr_or_null(b),
                      y.data_ptr(), residual.has_value() ? h.data_ptr() : nullptr, mean.data_ptr<float>(),
                      rstd.data_ptr<float>(), rows, (int)d, (float)eps, cur_stream(x));
@@ -139,11 +165,18 @@ std::vector<Tensor> layernorm_fwd(const Tensor& x, const optional<Tensor>& resid
 
 std::vector<Tensor> layernorm_bwd(const Tensor& dy, const Tensor& h, const Tensor& w, const Tensor& mean,
                                   const Tensor& rstd, const optional<Tensor>& dres) {
-  check_contig(dy, "dy");
-  check_contig(h, "h");
-  c10::OptionalDeviceGuard g(dy.device());
-  const int64_t d = h.size(-1), rows = h.numel() / d;
+  const int64_t d = check_norm_rows(h, "h"), rows = h.numel() / d;
+  check_norm_like(dy, h, "dy");
+  check_norm_param(w, h, d, "w");
+  check_norm_stat(mean, h, rows, "mean");
+  check_norm_stat(rstd, h, rows, "rstd");
+  if (dres.has_value()) check_norm_like(*dres, h, "dres");
+  c10::OptionalDeviceGuard g(h.device());
   auto dx = at::empty_like(h);
+  if (rows == 0) {
+    auto z = at::zeros({d}, h.options().dtype(at::kFloat));
+    return {dx, z, at::zeros_like(z)};
+  }
   auto dw = at::empty({d}, h.options().dtype(at::kFloat));
   auto db = at::empty({d}, h.options().dtype(at::kFloat));
   auto ws = at::empty({grt::norm_bwd_workspace_floats(rows, (int)d)}, h.options().dtype(at::kFloat));

@@ -24,6 +24,9 @@ void rmsnorm_bwd(DType dt, const void* dy, const void* h, const void* w, const f
                  const void* dres, void* dx, float* dw_f32, float* ws, int64_t rows, int d,
                  hipStream_t s, void* dw_t = nullptr, int accumulate = 0);
 int64_t norm_bwd_workspace_floats(int64_t rows, int d);
+// Widest supported row in 16-byte chunks (d * sizeof(T) / 16 <= norm_max_chunks(): d <= 16384 in
+// bf16, 8192 in fp32). The launchers do not check it: a caller must refuse wider rows.
+int norm_max_chunks();
 void layernorm_fwd(DType dt, const void* x, const void* residual, const void* w, const void* b,
                    void* y, void* h_out, float* mean, float* rstd, int64_t rows, int d, float eps,
                    hipStream_t s);

@@ -11,7 +11,9 @@
 //     so the decoder layer never runs a separate elementwise add;
 //   * backward keeps the weight-gradient partial sums in registers across the rows a
 //     workgroup visits and writes one fp32 slab per workgroup; a second tiny kernel sums the
-//     slabs column-wise (no float atomics, bitwise reproducible).
+//     slabs column-wise (no float atomics, bitwise reproducible);
+//   * a row is at most kNormMaxChunks = 2048 16-byte chunks wide (d <= 16384 in bf16, 8192 in
+//     fp32); the launchers do not check it, the bindings refuse wider rows (norm_max_chunks()).
 #include <stdlib.h>
 
 #include "grt_common.h"
@@ -249,6 +251,14 @@ __global__ __launch_bounds__(kNT) void colsum_kernel(const float* __restrict__ w
   }
 }
 
+// Widest row either dispatch ladder below covers, in 16-byte chunks: the last forward template
+// holds 32 chunks per lane (x 64 lanes), the last backward template 8 per thread (x 256 threads).
+// A wider row would silently drop its tail, so the bindings refuse it (norm_max_chunks()).
+constexpr int kNormMaxFwdPerLane = 32;
+constexpr int kNormMaxBwdPerThr = 8;
+constexpr int kNormMaxChunks = kNormMaxFwdPerLane * kWave;
+static_assert(kNormMaxChunks == kNormMaxBwdPerThr * kNT, "forward and backward ladders cover the same width");
+
 template <typename T, bool RMS>
 void launch_fwd(const void* x, const void* res, const void* w, const void* b, void* y, void* h_out,
                 float* mean, float* rstd, int64_t rows, int d, float eps, hipStream_t s, int64_t ldy = 0) {
@@ -271,7 +281,7 @@ void launch_fwd(const void* x, const void* res, const void* w, const void* b, vo
   else if (per_lane <= 4) GRT_NF(4);
   else if (per_lane <= 8) GRT_NF(8);
   else if (per_lane <= 16) GRT_NF(16);
-  else GRT_NF(32);
+  else GRT_NF(kNormMaxFwdPerLane);
 #undef GRT_NF
 #undef GRT_NF4
 }
@@ -310,7 +320,7 @@ void launch_bwd(const void* dy, const void* h, const void* w, const float* mean,
   if (per_thr <= 1) GRT_NB(1);
   else if (per_thr <= 2) GRT_NB(2);
   else if (per_thr <= 4) GRT_NB(4);
-  else GRT_NB(8);
+  else GRT_NB(kNormMaxBwdPerThr);
 #undef GRT_NB
 #undef GRT_NB2
   if (ws == nullptr) return;
@@ -327,6 +337,8 @@ void launch_bwd(const void* dy, const void* h, const void* w, const float* mean,
 }
 
 }  // namespace
+
+int norm_max_chunks() { return kNormMaxChunks; }
 
 int64_t norm_bwd_workspace_floats(int64_t rows, int d) { return (int64_t)bwd_blocks(rows) * 2 * d; }
 

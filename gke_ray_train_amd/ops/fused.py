@@ -41,10 +41,11 @@ class _RMSNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, rstd = ctx.saved_tensors
+        wc = w.contiguous()  # w itself is saved: it carries the gradient slot
         if not ctx.needs_input_grad[1]:  # frozen weight (LoRA / QLoRA): dX only
-            return _native.kernels().rmsnorm_bwd_dx(dy.contiguous(), x, w, rstd, None), None, None, None
+            return _native.kernels().rmsnorm_bwd_dx(dy.contiguous(), x, wc, rstd, None), None, None, None
         dx, dw = _norm_bwd_into_slot(w, lambda out, acc: _native.kernels().rmsnorm_bwd(
-            dy.contiguous(), x, w, rstd, None, out, acc))
+            dy.contiguous(), x, wc, rstd, None, out, acc))
         return dx, dw, None, None
 
 
@@ -78,12 +79,13 @@ class _AddRMSNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dh):
         h, w, rstd = ctx.saved_tensors
+        wc = w.contiguous()
         dy = torch.zeros_like(h) if dy is None else dy.contiguous()
         dres = None if dh is None else dh.contiguous()
         if not ctx.needs_input_grad[2]:  # frozen weight (LoRA / QLoRA): dX only
-            dx = _native.kernels().rmsnorm_bwd_dx(dy, h, w, rstd, dres)
+            dx = _native.kernels().rmsnorm_bwd_dx(dy, h, wc, rstd, dres)
             return dx, dx, None, None, None
-        dx, dw = _norm_bwd_into_slot(w, lambda out, acc: _native.kernels().rmsnorm_bwd(dy, h, w, rstd, dres, out, acc))
+        dx, dw = _norm_bwd_into_slot(w, lambda out, acc: _native.kernels().rmsnorm_bwd(dy, h, wc, rstd, dres, out, acc))
         return dx, dx, dw, None, None
 
 
@@ -109,8 +111,9 @@ class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, w, b, eps):
         C = _native.kernels()
+        w = w.contiguous()  # the backward kernel reads the saved weight as a dense [d] vector
         y, h, mean, rstd = C.layernorm_fwd(x.contiguous(), None if residual is None else residual.contiguous(),
-                                           w.contiguous(), None if b is None else b.contiguous(), eps)
+                                           w, None if b is None else b.contiguous(), eps)
         ctx.has_res = residual is not None
         ctx.has_b = b is not None
         ctx.save_for_backward(h, w, mean, rstd)
