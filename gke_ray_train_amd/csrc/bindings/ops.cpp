@@ -647,17 +647,36 @@ Tensor ce_bwd(const Tensor& logits, const Tensor& labels, const Tensor& lse, con
 }
 
 // ------------------------------------------------------------------ optimizer
+// The optimizer kernels size every access from p (or x) alone and read their small fp32 operands at
+// fixed indices (hyper[0..9], gscale[1], ws[0..nparts), out[0..1], a_ptr[0]), so each binding checks
+// every operand on the host before the launch.
+
+// a small fp32 operand: contiguous, at least min_numel values, on the device of the tensor `on`
+void check_optim_f32(const Tensor& t, const Tensor& on, int64_t min_numel, const char* name, const char* on_name) {
+  check_contig(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.numel() >= min_numel && t.device() == on.device(), name,
+              " must hold at least ", min_numel, " fp32 value(s) on the device of ", on_name, " (got ", t.numel(),
+              " of ", t.scalar_type(), " on ", t.device(), ")");
+}
+void check_optim_device(const Tensor& t, const Tensor& on, const char* name, const char* on_name) {
+  TORCH_CHECK(t.device() == on.device(), name, " must be on the device of ", on_name, " (", t.device(), " vs ",
+              on.device(), ")");
+}
+constexpr const char* kHyperDoc = "hyper (lr, b1, b2, eps, wd, bc1, bc2, gscale, stochastic_rounding, step)";
+
 int64_t sumsq_blocks() { return grt::optim_sumsq_blocks(); }
 void sumsq(const Tensor& x, Tensor& ws, int64_t slot) {
   check_contig(x, "x");
-  check_contig(ws, "ws");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= (slot + 1) * grt::optim_sumsq_blocks(), "ws too small");
+  TORCH_CHECK(slot >= 0, "sumsq: slot must be >= 0, got ", slot);
+  check_optim_f32(ws, x, (slot + 1) * grt::optim_sumsq_blocks(), "sumsq: ws", "x");
   c10::OptionalDeviceGuard g(x.device());
   grt::sumsq_accumulate(dtype_of(x), x.data_ptr(), x.numel(), ws.data_ptr<float>(), (int)slot, cur_stream(x));
 }
 void clip_finalize(const Tensor& ws, int64_t nparts, double max_norm, double prescale, Tensor& out) {
   check_contig(ws, "ws");
-  TORCH_CHECK(out.scalar_type() == at::kFloat && out.numel() >= 2, "out must be fp32 [2]");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat, "clip_finalize: ws must be fp32, got ", ws.scalar_type());
+  TORCH_CHECK(nparts >= 0 && nparts <= ws.numel(), "clip_finalize: nparts ", nparts, " outside ws [", ws.numel(), "]");
+  check_optim_f32(out, ws, 2, "clip_finalize: out", "ws");
   c10::OptionalDeviceGuard g(ws.device());
   grt::clip_coef_finalize(ws.data_ptr<float>(), (int)nparts, (float)max_norm, (float)prescale, out.data_ptr<float>(),
                           cur_stream(ws));
@@ -672,8 +691,11 @@ void adamw(Tensor& p, const Tensor& gr, Tensor& m, Tensor& v, const optional<Ten
   const int64_t n = p.numel();
   TORCH_CHECK(gr.numel() == n && m.numel() == n && v.numel() == n, "adamw size mismatch");
   TORCH_CHECK(m.scalar_type() == at::kFloat && v.scalar_type() == at::kFloat, "adam state must be fp32");
-  TORCH_CHECK(hyper.scalar_type() == at::kFloat && hyper.numel() >= 10 && hyper.is_cuda(),
-              "hyper fp32[10] on device: lr, b1, b2, eps, wd, bc1, bc2, gscale, stochastic_rounding, step");
+  check_optim_device(gr, p, "adamw: g", "p");
+  check_optim_device(m, p, "adamw: m", "p");
+  check_optim_device(v, p, "adamw: v", "p");
+  check_optim_f32(hyper, p, 10, kHyperDoc, "p");
+  if (gscale.has_value()) check_optim_f32(*gscale, p, 2, "adamw: gscale ([norm, coefficient])", "p");
   for (const Tensor* t : std::initializer_list<const Tensor*>{&p, &gr, &m, &v})
     TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0 ||
                     (t->element_size() == 2 && reinterpret_cast<uintptr_t>(t->data_ptr()) % 8 == 0),
@@ -681,6 +703,7 @@ void adamw(Tensor& p, const Tensor& gr, Tensor& m, Tensor& v, const optional<Ten
   if (master.has_value()) {
     check_contig(*master, "master");
     TORCH_CHECK(master->numel() == n && master->scalar_type() == at::kFloat, "master fp32 [n]");
+    check_optim_device(*master, p, "adamw: master", "p");
   }
   c10::OptionalDeviceGuard g(p.device());
   grt::adamw_step(dtype_of(p), dtype_of(gr), p.data_ptr(), gr.data_ptr(), m.data_ptr<float>(), v.data_ptr<float>(),
@@ -698,7 +721,10 @@ void adamw_t(Tensor& p, const Tensor& gr, Tensor& m, Tensor& v, const Tensor& hy
   TORCH_CHECK(m.scalar_type() == at::kFloat && v.scalar_type() == at::kFloat, "adamw_t: fp32 moments");
   TORCH_CHECK(gr.numel() == p.numel() && m.numel() == p.numel() && v.numel() == p.numel(), "adamw_t: sizes");
   TORCH_CHECK(pt.dim() == 2 && pt.size(0) == p.size(1) && pt.size(1) == p.size(0), "adamw_t: pt must be [cols, rows]");
-  TORCH_CHECK(hyper.scalar_type() == at::kFloat && hyper.numel() >= 10 && hyper.is_cuda(), "hyper fp32[10] on device");
+  for (const Tensor* t : std::initializer_list<const Tensor*>{&gr, &m, &v, &pt})
+    check_optim_device(*t, p, "adamw_t: g / m / v / pt", "p");
+  check_optim_f32(hyper, p, 10, kHyperDoc, "p");
+  if (gscale.has_value()) check_optim_f32(*gscale, p, 2, "adamw_t: gscale ([norm, coefficient])", "p");
   TORCH_CHECK(index_offset >= 0 && index_offset % 4 == 0, "adamw_t: index_offset must be a multiple of 4");
   for (const Tensor* t : std::initializer_list<const Tensor*>{&p, &gr, &m, &v, &pt})
     TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "adamw_t operands must be 16-byte aligned");
@@ -710,6 +736,7 @@ void adamw_t(Tensor& p, const Tensor& gr, Tensor& m, Tensor& v, const Tensor& hy
 
 void scale_(Tensor& x, double a, const optional<Tensor>& a_ptr) {
   check_contig(x, "x");
+  if (a_ptr.has_value()) check_optim_f32(*a_ptr, x, 1, "scale_: a_ptr", "x");
   c10::OptionalDeviceGuard g(x.device());
   grt::scale_inplace(dtype_of(x), x.data_ptr(), x.numel(), (float)a,
                      a_ptr.has_value() ? a_ptr->data_ptr<float>() : nullptr, cur_stream(x));
