@@ -1001,19 +1001,32 @@ void rope_attn_bwd_d64(const Tensor& dout, const Tensor& qkv, const Tensor& cos,
   grt::rope_attn_bwd_d64(p, cur_stream(qkv));
 }
 
-Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& seqlens_k, double scale) {
+// Split-K decode attention (decode_attention.hip). D is the binding's head dim: attn_decode is the
+// head_dim-128 entry point and refuses anything else, attn_decode_d64 the head_dim-64 one.
+Tensor attn_decode_impl(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& seqlens_k,
+                        double scale, int64_t D, const char* op, std::vector<Tensor>* partials = nullptr) {
   check_bshd(q, "q");
   check_bshd(k, "k");
   check_bshd(v, "v");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16,
-              "attn_decode: bf16");
-  TORCH_CHECK(q.size(3) == 128 && k.size(3) == 128 && v.size(3) == 128, "attn_decode: head_dim 128");
-  TORCH_CHECK(q.size(1) == 1, "attn_decode: one query token per sequence");
-  TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0), "attn_decode: k/v shapes");
+              op, ": bf16");
+  TORCH_CHECK(q.size(3) == D && k.size(3) == D && v.size(3) == D, op, ": head_dim ", D);
+  TORCH_CHECK(q.size(1) == 1, op, ": one query token per sequence");
+  TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0), op, ": k/v shapes");
   const int64_t Hq = q.size(2), Hkv = k.size(2);
-  TORCH_CHECK(Hq % Hkv == 0, "attn_decode: Hq % Hkv");
+  TORCH_CHECK(Hq % Hkv == 0, op, ": Hq % Hkv");
   const int64_t G = Hq / Hkv;
-  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "attn_decode: GQA group must be 1, 2, 4 or 8");
+  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, op, ": GQA group must be 1, 2, 4 or 8");
+  if (D == 64) {
+    // the kernel reads q / k / v with 16-byte loads at any (batch, key, head) offset
+    for (const Tensor* t : {&q, &k, &v}) {
+      TORCH_CHECK(t->device() == q.device(), op, ": q / k / v on one device");
+      TORCH_CHECK(t->stride(0) % 8 == 0 && t->stride(1) % 8 == 0 && t->stride(2) % 8 == 0 && t->stride(3) == 1,
+                  op, ": every stride a multiple of 8 elements, unit head_dim stride");
+      TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, op, ": 16-byte aligned base pointers");
+    }
+    TORCH_CHECK(k.size(1) <= INT32_MAX && q.size(0) * Hq <= INT32_MAX, op, ": dims");
+  }
   c10::OptionalDeviceGuard g(q.device());
   grt::AttnDecodeParams p{};
   p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr();
@@ -1024,20 +1037,46 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const opti
   p.v_bs = v.stride(0); p.v_ss = v.stride(1); p.v_hs = v.stride(2);
   p.o_bs = o.stride(0); p.o_hs = o.stride(2);
   p.B = (int)q.size(0); p.Hq = (int)Hq; p.Hkv = (int)Hkv; p.Sk = (int)k.size(1);
-  p.NS = grt::attn_decode_splits(p.B, p.Hkv, p.Sk);
+  p.NS = grt::attn_decode_splits(p.B, p.Hkv, p.Sk, (int)D);
   p.seqlens_k = nullptr;
   if (seqlens_k.has_value()) {
     check_contig(*seqlens_k, "seqlens_k");
     TORCH_CHECK(seqlens_k->scalar_type() == at::kInt && seqlens_k->numel() == q.size(0), "seqlens_k int32 [B]");
+    if (D == 64) TORCH_CHECK(seqlens_k->device() == q.device(), op, ": seqlens_k on q's device");
     p.seqlens_k = seqlens_k->data_ptr<int32_t>();
   }
   p.scale_log2 = (float)(scale * 1.4426950408889634);
-  auto ws = at::empty({(int64_t)p.B * Hq * p.NS * (128 + 2)}, q.options().dtype(at::kFloat));
+  auto ws = at::empty({(int64_t)p.B * Hq * p.NS * (D + 2)}, q.options().dtype(at::kFloat));
   p.part_o = ws.data_ptr<float>();
-  p.part_m = p.part_o + (int64_t)p.B * Hq * p.NS * 128;
+  p.part_m = p.part_o + (int64_t)p.B * Hq * p.NS * D;
   p.part_l = p.part_m + (int64_t)p.B * Hq * p.NS;
-  grt::attn_decode(p, cur_stream(q));
+  if (D == 64) grt::attn_decode_d64(p, cur_stream(q));
+  else grt::attn_decode(p, cur_stream(q));
+  if (partials) {
+    const int64_t n = (int64_t)p.B * Hq * p.NS;
+    *partials = {ws.narrow(0, 0, n * D).view({p.B, Hq, p.NS, D}), ws.narrow(0, n * D, n).view({p.B, Hq, p.NS}),
+                 ws.narrow(0, n * D + n, n).view({p.B, Hq, p.NS})};
+  }
   return o;
+}
+
+Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& seqlens_k, double scale) {
+  return attn_decode_impl(q, k, v, seqlens_k, scale, 128, "attn_decode");
+}
+
+Tensor attn_decode_d64(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& seqlens_k,
+                       double scale) {
+  return attn_decode_impl(q, k, v, seqlens_k, scale, 64, "attn_decode_d64");
+}
+
+// test support: attn_decode_d64 plus its per-split partial states, [o, part_o [B, Hq, NS, 64],
+// part_m [B, Hq, NS] (log2 units), part_l [B, Hq, NS]]; the partials are written only when NS > 1
+std::vector<Tensor> attn_decode_d64_partials(const Tensor& q, const Tensor& k, const Tensor& v,
+                                             const optional<Tensor>& seqlens_k, double scale) {
+  std::vector<Tensor> parts;
+  Tensor o = attn_decode_impl(q, k, v, seqlens_k, scale, 64, "attn_decode_d64", &parts);
+  parts.insert(parts.begin(), o);
+  return parts;
 }
 
 // ------------------------------------------------------------------ NF4
@@ -1182,8 +1221,9 @@ Tensor gemv(const Tensor& x, const Tensor& w, bool swiglu) {
 //   g given: y = bf16(x * rstd * g) W^T with rstd from sumsq[slot] (x = the residual stream h);
 //   res given: y = bf16(x W^T) + res, its sums of squares added into sumsq[slot], sumsq[1 - slot]
 //   zeroed for the next producer.
-//   cos given (qkv, head_dim 128): RoPE in the epilogue at position pos[m]; returns q [M, hq, 128],
-//   k / v written to cache slot pos[m] of kc / vc (rope_append semantics: bad positions write nothing).
+//   cos given (qkv, head_dim D = 2 * cos.size(-1), 128 or 64): RoPE in the epilogue at position
+//   pos[m]; returns q [M, hq, D], k / v written to cache slot pos[m] of kc / vc (rope_append
+//   semantics: bad positions write nothing).
 Tensor gemv_fused(const Tensor& x, const Tensor& w, const Tensor& sumsq, int64_t slot, bool swiglu,
                   const c10::optional<Tensor>& g, const c10::optional<Tensor>& res, double eps,
                   const c10::optional<Tensor>& cos, const c10::optional<Tensor>& sin, const c10::optional<Tensor>& pos,
@@ -1215,21 +1255,26 @@ Tensor gemv_fused(const Tensor& x, const Tensor& w, const Tensor& sumsq, int64_t
   Tensor q;
   if (rope) {
     TORCH_CHECK(sin.has_value() && pos.has_value() && kc.has_value() && vc.has_value(), "gemv_fused: rope needs sin / pos / kc / vc");
-    check_rope(*cos, *sin, *pos, M, cos->numel() / 64, 128);
-    TORCH_CHECK(hq > 0 && hkv > 0 && N == (hq + 2 * hkv) * 128, "gemv_fused: rope N == (hq + 2 hkv) * 128");
+    // the head dim is the table's: cos / sin rows hold D / 2 angles
+    TORCH_CHECK(cos->dim() >= 1 && (cos->size(-1) == 64 || cos->size(-1) == 32),
+                "gemv_fused: rope head_dim (2 * cos.size(-1)) must be 128 or 64");
+    const int64_t D = 2 * cos->size(-1);
+    check_rope(*cos, *sin, *pos, M, cos->numel() / (D / 2), D);
+    TORCH_CHECK(hq > 0 && hkv > 0 && N == (hq + 2 * hkv) * D, "gemv_fused: rope N == (hq + 2 hkv) * head_dim (", D, ")");
     for (const Tensor* c : {&*kc, &*vc}) {
       check_cuda(*c, "cache");
-      TORCH_CHECK(c->dim() == 4 && c->size(0) == M && c->size(2) == hkv && c->size(3) == 128 && c->stride(3) == 1 &&
+      TORCH_CHECK(c->dim() == 4 && c->size(0) == M && c->size(2) == hkv && c->size(3) == D && c->stride(3) == 1 &&
                       c->scalar_type() == at::kBFloat16,
-                  "gemv_fused: cache bf16 [M, L, hkv, 128]");
+                  "gemv_fused: cache bf16 [M, L, hkv, head_dim]");
     }
     TORCH_CHECK(vc->sizes() == kc->sizes(), "gemv_fused: kc / vc shapes");
-    q = at::empty({M, hq, 128}, x.options());
+    q = at::empty({M, hq, D}, x.options());
     f.q_out = q.data_ptr(), f.kc = kc->data_ptr(), f.vc = vc->data_ptr();
     f.c_bs = kc->stride(0), f.c_ss = kc->stride(1), f.c_hs = kc->stride(2);
     f.v_bs = vc->stride(0), f.v_ss = vc->stride(1), f.v_hs = vc->stride(2);
     f.cosb = cos->data_ptr<float>(), f.sinb = sin->data_ptr<float>(), f.pos = pos->data_ptr<int32_t>();
-    f.rope_S = (int)(cos->numel() / 64), f.cache_L = (int)kc->size(1), f.hq = (int)hq, f.hkv = (int)hkv;
+    f.rope_S = (int)(cos->numel() / (D / 2)), f.cache_L = (int)kc->size(1), f.hq = (int)hq, f.hkv = (int)hkv;
+    f.head_dim = (int)D;
   }
   if (normx) {
     TORCH_CHECK(!swiglu, "gemv_fused: normx and swiglu are exclusive");
@@ -1576,6 +1621,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cos") = py::none(), py::arg("sin") = py::none(), py::arg("pos") = py::none(),
         py::arg("kc") = py::none(), py::arg("vc") = py::none(), py::arg("hq") = 0, py::arg("hkv") = 0);
   m.def("attn_decode", &attn_decode);
+  m.def("attn_decode_d64", &attn_decode_d64);
+  m.def("attn_decode_d64_partials", &attn_decode_d64_partials,
+        "test support: attn_decode_d64 and its per-split (o, max, sum) partial states");
   m.def("embedding_fwd", &embedding_fwd);
   m.def("embedding_bwd", &embedding_bwd);
   m.def("gemm_wgrad", &gemm_wgrad, py::arg("x"), py::arg("y"), py::arg("out"), py::arg("accumulate"),

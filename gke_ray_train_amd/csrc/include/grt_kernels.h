@@ -229,7 +229,9 @@ struct AttnBwdParams {
 };
 void attn_bwd(const AttnBwdParams& p, hipStream_t s);
 int64_t attn_bwd_workspace_floats(int B, int Hq, int Sq, int D);
-// decode (Sq = 1) split-K attention (decode_attention.hip): bf16, head_dim 128, Hq / Hkv in {1,2,4,8}
+// decode (Sq = 1) split-K attention (decode_attention.hip): bf16, Hq / Hkv in {1,2,4,8}; head_dim 128
+// (attn_decode) or 64 (attn_decode_d64), NS = attn_decode_splits(.., head_dim), workspace
+// B * Hq * NS * (head_dim + 2) floats (unused at head_dim 64 when NS == 1: one launch, no combine)
 struct AttnDecodeParams {
   const void* q; const void* k; const void* v; void* o;
   int64_t q_bs, q_hs, k_bs, k_ss, k_hs, v_bs, v_ss, v_hs, o_bs, o_hs;
@@ -238,8 +240,9 @@ struct AttnDecodeParams {
   float scale_log2;           // softmax scale * log2(e)
   float* part_o; float* part_m; float* part_l;  // workspace [B, Hq, NS, (D | 1 | 1)]
 };
-int attn_decode_splits(int B, int Hkv, int Sk);
+int attn_decode_splits(int B, int Hkv, int Sk, int head_dim = 128);
 void attn_decode(const AttnDecodeParams& p, hipStream_t s);
+void attn_decode_d64(const AttnDecodeParams& p, hipStream_t s);
 // exact-fp32 variants (attention_f32.hip): same params with fp32 tensors, head_dim 64 or 128
 bool attn_f32_supported(int head_dim);
 void attn_fwd_f32(const AttnParams& p, hipStream_t s);
@@ -367,8 +370,9 @@ struct GemvFused {
   int64_t ldr;
   unsigned long long* sumsq_out;
   unsigned long long* sumsq_zero;
-  // q_out != null (qkv projection, head_dim 128, N = (hq + 2 hkv) * 128): RoPE at position pos[m]
-  // in the epilogue; q -> q_out [M, hq, 128], k / v -> cache slot pos[m] of kc / vc [B, L, hkv, 128]
+  // q_out != null (qkv projection, D = head_dim 128 or 64, N = (hq + 2 hkv) * D): RoPE at position
+  // pos[m] in the epilogue; q -> q_out [M, hq, D], k / v -> cache slot pos[m] of kc / vc
+  // [B, L, hkv, D]; cosb / sinb rows of D / 2
   void* q_out;
   void* kc;
   void* vc;
@@ -376,7 +380,7 @@ struct GemvFused {
   const float* cosb;
   const float* sinb;
   const int* pos;
-  int rope_S, cache_L, hq, hkv;
+  int rope_S, cache_L, hq, hkv, head_dim;
 };
 void gemv_fused_bf16(const GemvFused& f, hipStream_t s);
 int gemv_workgroups(int N);

@@ -1,4 +1,4 @@
-// Split-K attention for the decode step (one new query token per sequence), bf16, head_dim 128.
+// Split-K attention for the decode step (one new query token per sequence), bf16, head_dim 128 or 64.
 //
 // Reference role: the KV-cache decode of HF ``generate`` in the inference comparison
 // (reference ray-jobs/fine_tune_llama_ray.py:138-146). With Sq = 1 the
@@ -8,18 +8,20 @@
 // (max, sum, unnormalised output) for every query head of the GQA group; a second tiny kernel
 // merges the NS partials (log-sum-exp combine) and writes bf16.
 //
-// Lane mapping: 16 lanes per key (8 of the 128 dims each, one 16-byte load of K and of V), 4 keys
-// per wave per step, 16 keys per workgroup per step; the GQA group's query rows stay in registers
-// (fp32). Partial states of the 4 key-lane-groups of a wave merge with shuffles, the 4 waves
-// through LDS. Empty splits (keys beyond the valid length) emit max = -inf, sum = 0.
+// Lane mapping: D / 8 lanes per key (8 of the D dims each, one 16-byte load of K and of V), so at
+// head_dim 128 16 lanes per key, 4 keys per wave per step, 16 keys per workgroup per step, and at
+// head_dim 64 (Llama-3.2-1B) 8 lanes per key, 8 keys per wave, 32 keys per workgroup per step; the
+// GQA group's query rows stay in registers (fp32). Partial states of the key-lane-groups of a wave
+// merge with shuffles (lane offsets D / 8 .. 32), the 4 waves through LDS. Empty splits (keys
+// beyond the valid length) emit max = -inf, sum = 0. The kernels are templates on D; every
+// constant below is the head_dim-128 kernel's own at D = 128. At head_dim 64 a short cache
+// (Sk <= kSingleSplitKeys) is one split that writes the output itself: below that length the
+// second launch costs more than the splits save.
 #include "grt_common.h"
 #include "grt_kernels.h"
 
 namespace grt {
 namespace {
-
-constexpr int D = 128;
-constexpr int kMaxG = 8;  // query heads per kv head handled per workgroup
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -31,24 +33,27 @@ __device__ __forceinline__ void cvt8(const u32x4& v, float (&f)[8]) {
   }
 }
 
-template <int G>
+template <int D, int G>
 __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecodeParams p) {
+  constexpr int kLanes = D / 8;           // lanes per key
+  constexpr int kWaveKeys = 64 / kLanes;  // keys per wave per step
+  constexpr int kStep = 4 * kWaveKeys;    // keys per workgroup per step
   __shared__ float sm_m[4][G], sm_l[4][G];
   __shared__ float sm_o[4][G][D];
   const int bh = blockIdx.x, split = blockIdx.y;
   const int b = bh / p.Hkv, hkv = bh % p.Hkv;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int grp = lane >> 4, c = lane & 15;  // key lane-group, 16-byte chunk of the head dim
+  const int grp = lane / kLanes, c = lane % kLanes;  // key lane-group, 16-byte chunk of the head dim
   int len = p.Sk;
   if (p.seqlens_k) len = min(len, p.seqlens_k[b]);
-  const int per = ((len + p.NS - 1) / p.NS + 15) / 16 * 16;
+  const int per = ((len + p.NS - 1) / p.NS + kStep - 1) / kStep * kStep;
   const int k0 = split * per, k1 = min(len, k0 + per);
 
   const bf16* Kb = (const bf16*)p.k + (int64_t)b * p.k_bs + (int64_t)hkv * p.k_hs + c * 8;
   const bf16* Vb = (const bf16*)p.v + (int64_t)b * p.v_bs + (int64_t)hkv * p.v_hs + c * 8;
   // the K / V stream is pipelined one step ahead, and its first loads are issued before the query
   // loads, so the two dependent round trips at the start overlap (most splits are 1-2 steps long)
-  int j = k0 + wave * 4 + grp;
+  int j = k0 + wave * kWaveKeys + grp;
   u32x4 kraw{}, vraw{};
   if (j < k1) {
     kraw = *reinterpret_cast<const u32x4*>(Kb + (int64_t)j * p.k_ss);
@@ -70,13 +75,13 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
 #pragma unroll
     for (int i = 0; i < 8; ++i) o[g][i] = 0.f;
   }
-  for (; j < k1; j += 16) {
+  for (; j < k1; j += kStep) {
     float kf[8], vf[8];
     cvt8(kraw, kf);
     cvt8(vraw, vf);
-    if (j + 16 < k1) {
-      kraw = *reinterpret_cast<const u32x4*>(Kb + (int64_t)(j + 16) * p.k_ss);
-      vraw = *reinterpret_cast<const u32x4*>(Vb + (int64_t)(j + 16) * p.v_ss);
+    if (j + kStep < k1) {
+      kraw = *reinterpret_cast<const u32x4*>(Kb + (int64_t)(j + kStep) * p.k_ss);
+      vraw = *reinterpret_cast<const u32x4*>(Vb + (int64_t)(j + kStep) * p.v_ss);
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -84,7 +89,7 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
 #pragma unroll
       for (int i = 0; i < 8; ++i) s = fmaf(q[g][i], kf[i], s);
 #pragma unroll
-      for (int off = 8; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+      for (int off = kLanes / 2; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
       const float mn = fmaxf(m[g], s);
       const float a = fast_exp2(m[g] - mn), e = fast_exp2(s - mn);
       l[g] = l[g] * a + e;
@@ -93,11 +98,11 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
       m[g] = mn;
     }
   }
-  // merge the 4 key lane-groups of the wave (lanes c, c+16, c+32, c+48 hold the same dims)
+  // merge the key lane-groups of the wave (lanes c, c + D/8, c + 2 D/8, ... hold the same dims)
 #pragma unroll
   for (int g = 0; g < G; ++g) {
 #pragma unroll
-    for (int off = 16; off <= 32; off <<= 1) {
+    for (int off = kLanes; off <= 32; off <<= 1) {
       const float m2 = __shfl_xor(m[g], off, 64), l2 = __shfl_xor(l[g], off, 64);
       const float mn = fmaxf(m[g], m2);
       const float a = mn == -INFINITY ? 0.f : fast_exp2(m[g] - mn);
@@ -127,17 +132,25 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
       ll += sm_l[w][g] * a;
       oo += sm_o[w][g][d] * a;
     }
+    if constexpr (D == 64) {
+      if (p.NS == 1) {  // short cache, one split: this is the whole softmax, no combine launch
+        bf16* op = (bf16*)p.o + (int64_t)b * p.o_bs + (int64_t)(hkv * G + g) * p.o_hs + d;
+        *op = static_cast<bf16>(ll > 0.f ? oo / ll : 0.f);
+        continue;
+      }
+    }
     const int64_t slot = ((int64_t)(b * p.Hq + hkv * G + g) * p.NS + split);
     p.part_o[slot * D + d] = oo;
     if (d == 0) { p.part_m[slot] = mm; p.part_l[slot] = ll; }
   }
 }
 
-// One workgroup per (batch, query head), one thread per head dim. The NS <= 64 partial states are
-// loaded by the lanes of wave 0 in parallel (max / weight / sum by butterflies, weights to LDS),
+// One workgroup per (batch, query head), one thread per head dim (D threads). The NS <= 64 partial
+// states are loaded by the lanes of wave 0 in parallel (max / weight / sum by butterflies, weights to LDS),
 // then every thread sums its dimension over the splits with independent loads — two dependent
 // round trips instead of a serial NS-long chain.
-__global__ __launch_bounds__(128) void attn_decode_combine_kernel(const AttnDecodeParams p) {
+template <int D>
+__global__ __launch_bounds__(D) void attn_decode_combine_kernel(const AttnDecodeParams p) {
   __shared__ float wts[64];
   __shared__ float lsum;
   const int bhq = blockIdx.x, d = threadIdx.x;
@@ -168,26 +181,43 @@ __global__ __launch_bounds__(128) void attn_decode_combine_kernel(const AttnDeco
   *op = static_cast<bf16>(ll > 0.f ? oo / ll : 0.f);
 }
 
+template <int D>
+void launch_decode(const AttnDecodeParams& p, hipStream_t s) {
+  const dim3 g1((unsigned)(p.B * p.Hkv), (unsigned)p.NS);
+  const int G = p.Hq / p.Hkv;
+  switch (G) {
+    case 1: hipLaunchKernelGGL((attn_decode_split_kernel<D, 1>), g1, dim3(256), 0, s, p); break;
+    case 2: hipLaunchKernelGGL((attn_decode_split_kernel<D, 2>), g1, dim3(256), 0, s, p); break;
+    case 4: hipLaunchKernelGGL((attn_decode_split_kernel<D, 4>), g1, dim3(256), 0, s, p); break;
+    default: hipLaunchKernelGGL((attn_decode_split_kernel<D, 8>), g1, dim3(256), 0, s, p); break;
+  }
+  if (D == 64 && p.NS == 1) return;  // the split kernel wrote the output itself
+  hipLaunchKernelGGL(attn_decode_combine_kernel<D>, dim3((unsigned)(p.B * p.Hq)), dim3(D), 0, s, p);
+}
+
+// head_dim 64: up to this many cached keys run as ONE split whose kernel normalises and writes the
+// bf16 output itself, with no combine launch. Llama-3.2-1B geometry, batch 1, back-to-back calls:
+// one launch 5.2 / 6.6 / 8.5 / 9.5 us at Sk 32 / 128 / 256 / 320 against 8.8-9.4 us for split +
+// combine at every such Sk and 5.9 / 7.1 / 10.9 / 12.9 us for the flash forward kernel
+// (profiles/decode_d64.md)
+constexpr int kSingleSplitKeys = 256;
+
 }  // namespace
 
-int attn_decode_splits(int B, int Hkv, int Sk) {
+// splits per (batch, kv head): ~512 workgroups in all, at least one workgroup step of keys (16 at
+// head_dim 128, 32 at head_dim 64) per split, at most 64 (the combine kernel's one wave of partials)
+int attn_decode_splits(int B, int Hkv, int Sk, int head_dim) {
+  if (head_dim == 64 && Sk <= kSingleSplitKeys) return 1;
+  const int step = 4 * (64 / (head_dim / 8));
   int ns = (512 + B * Hkv - 1) / (B * Hkv);
-  const int max_ns = (Sk + 15) / 16;
+  const int max_ns = (Sk + step - 1) / step;
   if (ns > max_ns) ns = max_ns;
   if (ns > 64) ns = 64;
   return ns < 1 ? 1 : ns;
 }
 
-void attn_decode(const AttnDecodeParams& p, hipStream_t s) {
-  const dim3 g1((unsigned)(p.B * p.Hkv), (unsigned)p.NS);
-  const int G = p.Hq / p.Hkv;
-  switch (G) {
-    case 1: hipLaunchKernelGGL(attn_decode_split_kernel<1>, g1, dim3(256), 0, s, p); break;
-    case 2: hipLaunchKernelGGL(attn_decode_split_kernel<2>, g1, dim3(256), 0, s, p); break;
-    case 4: hipLaunchKernelGGL(attn_decode_split_kernel<4>, g1, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL(attn_decode_split_kernel<8>, g1, dim3(256), 0, s, p); break;
-  }
-  hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)(p.B * p.Hq)), dim3(D), 0, s, p);
-}
+void attn_decode(const AttnDecodeParams& p, hipStream_t s) { launch_decode<128>(p, s); }
+
+void attn_decode_d64(const AttnDecodeParams& p, hipStream_t s) { launch_decode<64>(p, s); }
 
 }  // namespace grt

@@ -18,6 +18,7 @@
 //     the other of two accumulator sets, the one the next producer adds into;
 //   * EPI_ROPE (qkv): each wave's 4 rows are two RoPE pairs of one head, so q / k are rotated in
 //     the epilogue and written straight to the attention input and the KV cache (no rope_append);
+//     the head dim (128 or 64) is a template parameter;
 //   * PRO_NORMX (qkv, gate_up, lm_head): every wave sums the 64 accumulators (one load, a wave
 //     reduction), rstd = rsqrt(sum / K + eps), and the K loop feeds bf16(h * rstd * g) to the FMAs
 //     (the separate norm kernel's rounding).
@@ -71,13 +72,13 @@ struct GemvArgs {
   int64_t ldr;
   unsigned long long* sumsq_out;   // [M][kSumsqSlots], zero at launch
   unsigned long long* sumsq_zero;  // [M][kSumsqSlots], zeroed here for the next producer
-  // EPI_ROPE (the qkv projection, head_dim 128): q rotated into q_out [M, hq, 128], k rotated and v
-  // written at cache slot pos[m] of kc / vc (row m = batch row m)
+  // EPI_ROPE (the qkv projection, head_dim HD = 128 or 64): q rotated into q_out [M, hq, HD], k
+  // rotated and v written at cache slot pos[m] of kc / vc (row m = batch row m)
   bf16* q_out;
   bf16* kc;
   bf16* vc;
   int64_t c_bs, c_ss, c_hs, v_bs, v_ss, v_hs;
-  const float* cosb;  // [>= rope_S, 64]
+  const float* cosb;  // [>= rope_S, HD / 2]
   const float* sinb;
   const int* pos;     // [M]
   int rope_S, cache_L, hq, hkv;
@@ -88,7 +89,7 @@ struct GemvArgs {
 // exposed — o_proj ran at 3.5 TB/s).
 // PRO_SWI: x is the fused [gate | up] projection output [M, 2K]; the kernel multiplies by
 // silu(gate) * up on the fly (the decode MLP's SwiGLU folded into the down-projection GEMV).
-template <int M, int KS, int PRO, int EPI>
+template <int M, int KS, int PRO, int EPI, int HD = 128>
 __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
   constexpr bool SWI = PRO == PRO_SWI;
   __shared__ float red[4][M][kR];
@@ -96,10 +97,11 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
   const int slot = wave / KS, kp = wave % KS;
   const int n0 = (blockIdx.x * (4 / KS) + slot) * kR;
   const int N = a.N, K = a.K;
-  // EPI_ROPE: the wave's 4 rows are the RoPE pairs (d, d + 64), (d + 1, d + 65) of one head, so the
-  // rotation happens in the epilogue: rows hh*128 + {d, d+1, d+64, d+65}, d = 2 * (group % 32)
-  const int hh = n0 / 128, d0 = 2 * ((n0 / kR) % 32);
-  auto row_of = [&](int r) { return EPI == EPI_ROPE ? hh * 128 + d0 + (r & 1) + 64 * (r >> 1) : n0 + r; };
+  // EPI_ROPE: the wave's 4 rows are the RoPE pairs (d, d + HD/2), (d + 1, d + HD/2 + 1) of one head,
+  // so the rotation happens in the epilogue: rows hh*HD + {d, d+1, d+HD/2, d+HD/2+1},
+  // d = 2 * (group % (HD/4))
+  const int hh = n0 / HD, d0 = 2 * ((n0 / kR) % (HD / 4));
+  auto row_of = [&](int r) { return EPI == EPI_ROPE ? hh * HD + d0 + (r & 1) + (HD / 2) * (r >> 1) : n0 + r; };
   const bf16* __restrict__ x = a.x;
   float acc[M][kR];
 #pragma unroll
@@ -212,11 +214,11 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
         if (hh < a.hq + a.hkv) {
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            const float cs = a.cosb[(int64_t)p * 64 + d0 + i], sn = a.sinb[(int64_t)p * 64 + d0 + i];
+            const float cs = a.cosb[(int64_t)p * (HD / 2) + d0 + i], sn = a.sinb[(int64_t)p * (HD / 2) + d0 + i];
             o[i] = y[i] * cs - y[i + 2] * sn;
             o[i + 2] = y[i + 2] * cs + y[i] * sn;
           }
-          dst = hh < a.hq ? a.q_out + ((int64_t)m * a.hq + hh) * 128
+          dst = hh < a.hq ? a.q_out + ((int64_t)m * a.hq + hh) * HD
                           : a.kc + m * a.c_bs + (int64_t)p * a.c_ss + (int64_t)(hh - a.hq) * a.c_hs;
         } else {
 #pragma unroll
@@ -224,7 +226,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
           dst = a.vc + m * a.v_bs + (int64_t)p * a.v_ss + (int64_t)(hh - a.hq - a.hkv) * a.v_hs;
         }
 #pragma unroll
-        for (int r = 0; r < kR; ++r) dst[d0 + (r & 1) + 64 * (r >> 1)] = static_cast<bf16>(o[r]);
+        for (int r = 0; r < kR; ++r) dst[d0 + (r & 1) + (HD / 2) * (r >> 1)] = static_cast<bf16>(o[r]);
       }
     }
   } else if constexpr (EPI == EPI_NONE) {
@@ -315,14 +317,14 @@ __global__ __launch_bounds__(64 * KS) void gemv_mfma_kernel(const bf16* __restri
   }
 }
 
-template <int PRO, int EPI>
+template <int PRO, int EPI, int HD = 128>
 void launch_gemv(const GemvArgs& a, int M, hipStream_t s) {
   const dim3 grid((unsigned)gemv_workgroups(a.N));
   switch (M) {
-    case 1: hipLaunchKernelGGL((gemv_kernel<1, kKS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((gemv_kernel<2, kKS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((gemv_kernel<3, kKS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((gemv_kernel<4, kKS, PRO, EPI>), grid, dim3(256), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((gemv_kernel<1, kKS, PRO, EPI, HD>), grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((gemv_kernel<2, kKS, PRO, EPI, HD>), grid, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((gemv_kernel<3, kKS, PRO, EPI, HD>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((gemv_kernel<4, kKS, PRO, EPI, HD>), grid, dim3(256), 0, s, a); break;
   }
 }
 
@@ -366,7 +368,10 @@ void gemv_fused_bf16(const GemvFused& f, hipStream_t s) {
   a.cosb = f.cosb, a.sinb = f.sinb, a.pos = f.pos, a.rope_S = f.rope_S, a.cache_L = f.cache_L;
   a.hq = f.hq, a.hkv = f.hkv;
   const bool normx = f.sumsq_in != nullptr, resnorm = f.res != nullptr, rope = f.q_out != nullptr;
-  if (rope && normx) launch_gemv<PRO_NORMX, EPI_ROPE>(a, f.M, s);
+  const bool d64 = f.head_dim == 64;  // the binding admits 128 or 64
+  if (rope && normx && d64) launch_gemv<PRO_NORMX, EPI_ROPE, 64>(a, f.M, s);
+  else if (rope && d64) launch_gemv<PRO_NONE, EPI_ROPE, 64>(a, f.M, s);
+  else if (rope && normx) launch_gemv<PRO_NORMX, EPI_ROPE>(a, f.M, s);
   else if (rope) launch_gemv<PRO_NONE, EPI_ROPE>(a, f.M, s);
   else if (normx && resnorm) launch_gemv<PRO_NORMX, EPI_RESNORM>(a, f.M, s);
   else if (normx) launch_gemv<PRO_NORMX, EPI_NONE>(a, f.M, s);

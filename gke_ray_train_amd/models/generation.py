@@ -150,7 +150,7 @@ def _norm_fusable(model, B: int) -> bool:
     norms = [m.norm] + [n for ly in m.layers for n in (ly.input_layernorm, ly.post_attention_layernorm)]
     lins = [model.lm_head] + [p for ly in m.layers for p in (ly.self_attn.qkv_proj, ly.self_attn.o_proj,
                                                                ly.mlp.gate_up_proj, ly.mlp.down_proj)]
-    if model.config.head_dim != 128:  # the RoPE epilogue / decode attention kernels
+    if model.config.head_dim not in (64, 128):  # the RoPE epilogue / decode attention kernels
         return False
     return (all(_plain_bf16_linear(p) for p in lins)
             and all(n.weight.dtype == torch.bfloat16 and n.weight.is_contiguous() and n.weight.data_ptr() % 16 == 0
@@ -194,7 +194,7 @@ class GraphDecoder:
 
     Usage: ``dec = GraphDecoder(model, B, max_len)``; ``logits = dec.prefill(ids)`` (eager, any
     prompt length); then ``logits = dec.step(next_ids)`` per token (graph replay). Needs a bf16
-    Llama on the GPU with head_dim 128 (the HIP RoPE / flash kernels)."""
+    Llama on the GPU with head_dim 128 or 64 (the HIP RoPE epilogue / decode attention kernels)."""
 
     def __init__(self, model, B: int, max_len: int):
         self.model = model
@@ -282,7 +282,7 @@ class GraphDecoder:
 def _graph_ok(model, input_ids) -> bool:
     p = next(model.parameters())
     cfg = model.config
-    return (input_ids.is_cuda and p.dtype == torch.bfloat16 and cfg.head_dim == 128
+    return (input_ids.is_cuda and p.dtype == torch.bfloat16 and cfg.head_dim in (64, 128)
             and _native.kernels_available())
 
 
@@ -293,9 +293,11 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              use_graph: Optional[bool] = None, sync_every: int = 16, **_):
     """Returns [B, prompt + generated] token ids (HF ``generate`` output convention).
 
-    The HIP-graph decoder (fused RoPE epilogue, split-K decode attention) is for bf16 models with
-    head_dim 128. A head_dim-64 model (``llama3.2-1b``) generates on the eager path: its one-token
-    attention over the cache runs on the head_dim-64 flash forward kernel with ``seqlens_k``."""
+    A bf16 model on the GPU with head_dim 128 or 64 (``llama3.2-1b``) decodes through the HIP-graph
+    decoder by default (fused RoPE epilogue of the qkv GEMV, split-K decode attention at either
+    width). ``use_graph=False`` gives the eager step; ``GRT_DECODE_ATTN=0`` sends the one-token
+    attention to the flash forward kernel with ``seqlens_k`` and ``GRT_GEMV_NORM=0`` keeps the
+    norms and ``rope_append`` outside the GEMVs."""
     was = model.training
     model.eval()
     B, S = input_ids.shape

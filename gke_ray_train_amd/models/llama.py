@@ -105,7 +105,8 @@ CONFIGS = {
                                           original_max_position_embeddings=8192), name="llama3.2-1b"),
     # small configs for tests / smoke. bf16 attention runs on HIP kernels at head_dim 128 (the fused
     # RoPE + attention path with its packed / transposed-output / graph-decode features) and at
-    # head_dim 64 (RoPE inside the qkv-native kernels, packed or not; no transposed side outputs):
+    # head_dim 64 (RoPE inside the qkv-native kernels, packed or not; no transposed side outputs;
+    # split-K decode attention, the RoPE GEMV epilogue and graph decode like head_dim 128):
     # llama-tiny-d64 covers the latter.
     "llama-tiny-d64": dict(vocab_size=512, hidden_size=256, intermediate_size=688, num_hidden_layers=2,
                            num_attention_heads=4, num_key_value_heads=2, max_position_embeddings=512,

@@ -273,12 +273,14 @@ def flash_attention(q, k, v, causal=True, scale=None, seqlens_k=None, dropout_p=
     if dropout_p > 0.0 and seed is None:
         seed = _dropout_seed()
     seed = 0 if seed is None else int(seed)
-    if (_gpu(q) and q.shape[1] == 1 and q.dtype == torch.bfloat16 and q.shape[-1] == 128 and dropout_p == 0.0
+    if (_gpu(q) and q.shape[1] == 1 and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128) and dropout_p == 0.0
             and not torch.is_grad_enabled() and (q.shape[2] // k.shape[2]) in (1, 2, 4, 8)
             and q.shape[2] % k.shape[2] == 0 and _DECODE_KERNEL):
         # one query token per sequence (decode): split-K kernel over the cached keys; every cached
         # key is at or before the query position, so the causal mask is the valid-length mask
-        return _native.kernels().attn_decode(q, k, v, seqlens_k, scale)
+        C = _native.kernels()
+        decode = C.attn_decode if q.shape[-1] == 128 else C.attn_decode_d64
+        return decode(q, k, v, seqlens_k, scale)
     if _gpu(q) and q.dtype in (torch.bfloat16, torch.float32) and q.shape[-1] in (64, 128):
         return _FlashAttn.apply(q, k, v, causal, scale, seqlens_k, float(dropout_p), seed)
     if _gpu(q):

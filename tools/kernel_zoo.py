@@ -127,6 +127,8 @@ kc = torch.randn(1, 4096, 8, 128, device=dev, dtype=bf)
 vc = torch.randn(1, 4096, 8, 128, device=dev, dtype=bf)
 sl = torch.full((1,), 4096, device=dev, dtype=torch.int32)
 rep(lambda: C.attn_decode(qd, kc, vc, sl, 128 ** -0.5))
+# the same at head_dim 64 (Llama-3.2-1B geometry): views of the same buffers
+rep(lambda: C.attn_decode_d64(qd[..., :64], kc[..., :64], vc[..., :64], sl, 64 ** -0.5))
 
 # NF4 dequant (Llama-3.1-8B gate_up weight) and its transposed variant
 wq = torch.randn(2 * 14336, 4096, device=dev, dtype=bf)
