@@ -1296,6 +1296,57 @@ Tensor gemv_fused(const Tensor& x, const Tensor& w, const Tensor& sumsq, int64_t
   return y;
 }
 
+// y [M, N] = x W^T straight from the NF4 codes of W [N, K] (gemv_nf4.hip; blocksize 64, fp32 absmax),
+// 1-4 rows. With h [M, r * targets], lora_b (target i: bf16 [n_i, r]) and lora_off (its first output
+// row): rows of target i also get scaling * h[:, i r : (i + 1) r] lora_b[i]^T.
+Tensor nf4_gemv(const Tensor& x, const Tensor& q, const Tensor& absmax, int64_t N, int64_t K,
+                const optional<Tensor>& h, const optional<std::vector<Tensor>>& lora_b,
+                const optional<std::vector<int64_t>>& lora_off, double scaling) {
+  check_cuda(x, "x");
+  check_contig(q, "qweight");
+  check_contig(absmax, "absmax");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == K, "nf4_gemv: x [M, K]");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "nf4_gemv: x bf16");
+  TORCH_CHECK(q.is_cuda() && absmax.is_cuda() && q.scalar_type() == at::kByte && absmax.scalar_type() == at::kFloat,
+              "nf4_gemv: qweight uint8, absmax fp32, on the GPU");
+  const int64_t M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= 4, "nf4_gemv: 1..4 rows");
+  TORCH_CHECK(N >= 1 && K >= 64 && K % 64 == 0 && N <= INT32_MAX && K <= (1 << 30), "nf4_gemv: K % 64 == 0");
+  TORCH_CHECK(q.numel() * 2 == N * K && absmax.numel() * 64 == N * K, "nf4_gemv: nf4 shapes (blocksize 64)");
+  TORCH_CHECK(x.stride(1) == 1 && x.stride(0) >= K && x.stride(0) % 8 == 0, "nf4_gemv: x row stride >= K, multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "nf4_gemv: 16-byte alignment");
+  grt::Nf4Gemv f{};
+  f.x = x.data_ptr(), f.ldx = x.stride(0), f.q = q.data_ptr<uint8_t>(), f.absmax = absmax.data_ptr<float>();
+  f.M = (int)M, f.N = (int)N, f.K = (int)K;
+  const bool lora = h.has_value() || lora_b.has_value() || lora_off.has_value();
+  if (lora) {
+    TORCH_CHECK(h.has_value() && lora_b.has_value() && lora_off.has_value(), "nf4_gemv: h, lora_b and lora_off go together");
+    const int64_t T = (int64_t)lora_b->size();
+    TORCH_CHECK(T >= 1 && T <= grt::kNf4GemvMaxTargets && (int64_t)lora_off->size() == T, "nf4_gemv: 1..4 targets");
+    const int64_t r = (*lora_b)[0].dim() == 2 ? (*lora_b)[0].size(1) : 0;
+    TORCH_CHECK(r >= 8 && r <= 64 && r % 8 == 0, "nf4_gemv: r <= 64, r % 8 == 0");
+    TORCH_CHECK(h->is_cuda() && h->dim() == 2 && h->scalar_type() == at::kBFloat16 && h->size(0) == M &&
+                    h->size(1) == r * T && h->stride(1) == 1, "nf4_gemv: h bf16 [M, r * targets]");
+    for (int64_t i = 0; i < T; ++i) {
+      const Tensor& b = (*lora_b)[i];
+      const int64_t off = (*lora_off)[i];
+      TORCH_CHECK(b.is_cuda() && b.dim() == 2 && b.scalar_type() == at::kBFloat16 && b.is_contiguous() && b.size(1) == r &&
+                      b.size(0) >= 1, "nf4_gemv: lora_b bf16 [n_i, r] contiguous");
+      TORCH_CHECK(off >= 0 && off % 4 == 0 && off + b.size(0) <= N, "nf4_gemv: lora_off % 4 == 0, target inside [0, N)");
+      for (int64_t j = 0; j < i; ++j)
+        TORCH_CHECK(off + b.size(0) <= f.off[j] || f.off[j] + f.n[j] <= off, "nf4_gemv: targets overlap");
+      f.b[i] = b.data_ptr(), f.off[i] = (int)off, f.n[i] = (int)b.size(0);
+    }
+    f.h = h->data_ptr(), f.ldh = h->stride(0), f.r = (int)r, f.targets = (int)T, f.scaling = (float)scaling;
+  }
+  c10::OptionalDeviceGuard g(x.device());
+  Tensor y = at::empty({M, N}, x.options());
+  f.y = y.data_ptr();
+  grt::gemv_nf4(f, cur_stream(x));
+  return y;
+}
+
 // ------------------------------------------------------------------ embedding
 Tensor embedding_fwd(const Tensor& ids, const Tensor& w) {
   check_contig(ids, "ids");
@@ -1620,6 +1671,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("swiglu") = false, py::arg("g") = py::none(), py::arg("res") = py::none(), py::arg("eps") = 1e-5,
         py::arg("cos") = py::none(), py::arg("sin") = py::none(), py::arg("pos") = py::none(),
         py::arg("kc") = py::none(), py::arg("vc") = py::none(), py::arg("hq") = 0, py::arg("hkv") = 0);
+  m.def("nf4_gemv", &nf4_gemv, py::arg("x"), py::arg("qweight"), py::arg("absmax"), py::arg("N"), py::arg("K"),
+        py::arg("h") = py::none(), py::arg("lora_b") = py::none(), py::arg("lora_off") = py::none(),
+        py::arg("scaling") = 1.0);
   m.def("attn_decode", &attn_decode);
   m.def("attn_decode_d64", &attn_decode_d64);
   m.def("attn_decode_d64_partials", &attn_decode_d64_partials,

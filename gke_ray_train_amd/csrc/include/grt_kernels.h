@@ -385,6 +385,28 @@ struct GemvFused {
 void gemv_fused_bf16(const GemvFused& f, hipStream_t s);
 int gemv_workgroups(int N);
 
+// ---------------- decode GEMV from NF4 codes (gemv_nf4.hip) ----------------
+// y[M, N] (bf16, contiguous) = x[M, K] W^T with W the exact NF4 values code[q] * absmax (blocksize
+// 64, the layout nf4_quantize writes); M <= 4, K % 64 == 0, x rows and q 16-byte aligned.
+// targets > 0: rows off[i] .. off[i] + n[i] - 1 also get scaling * h[m][i r .. i r + r - 1] . b[i][row - off[i]]
+// (b[i]: bf16 [n[i], r] contiguous; r <= 64; off[i] % 4 == 0).
+constexpr int kNf4GemvMaxTargets = 4;
+struct Nf4Gemv {
+  const void* x;
+  int64_t ldx;
+  const uint8_t* q;
+  const float* absmax;
+  void* y;
+  int M, N, K;
+  const void* h;
+  int64_t ldh;
+  int r, targets;
+  float scaling;
+  const void* b[kNf4GemvMaxTargets];
+  int off[kNf4GemvMaxTargets], n[kNf4GemvMaxTargets];
+};
+void gemv_nf4(const Nf4Gemv& f, hipStream_t s);
+
 // ---------------- xGMI peer-to-peer collectives (ipc_comm.hip) ----------------
 constexpr int kIpcMaxRanks = 8;
 constexpr int kIpcMaxBlocks = 64;

@@ -194,3 +194,15 @@ def nf4_dequantize(packed, absmax, n, blocksize=64, dtype=torch.bfloat16):
     idx = torch.stack([hi, lo], dim=1).view(-1)
     vals = code[idx].view(-1, blocksize) * absmax[:, None]
     return vals.view(-1)[:n].to(dtype)
+
+
+def nf4_gemv(x, packed, absmax, N, K, h=None, lora_b=None, lora_off=None, scaling=1.0):
+    """x [M, K] times the exact NF4 weight (fp32 level * fp32 absmax, blocksize 64), plus
+    scaling * h[:, i r:(i + 1) r] lora_b[i]^T on rows lora_off[i] ...; float64 sums, rounded once."""
+    w = nf4_dequantize(packed, absmax, N * K, 64, torch.float32).view(N, K)
+    y = x.double() @ w.double().t()
+    if lora_b:
+        r = lora_b[0].shape[1]
+        for i, (b, off) in enumerate(zip(lora_b, lora_off)):
+            y[:, off:off + b.shape[0]] += scaling * (h[:, i * r:(i + 1) * r].double() @ b.double().t())
+    return y.to(x.dtype)

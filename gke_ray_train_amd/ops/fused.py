@@ -572,3 +572,15 @@ def nf4_dequantize(packed, absmax, n, blocksize=64, dtype=torch.bfloat16, out=No
     if _gpu(packed):
         return _native.kernels().nf4_dequantize(packed, absmax, n, blocksize, dtype, out)
     return _ref.nf4_dequantize(packed, absmax, n, blocksize, dtype)
+
+
+def nf4_gemv(x, qweight, absmax, N, K, h=None, lora_b=None, lora_off=None, scaling=1.0):
+    """Decode GEMV from NF4 codes (gemv_nf4.hip): y [M, N] = x [M, K] W^T for 1-4 bf16 rows, W the
+    exact NF4 value (fp32 level * fp32 absmax, blocksize 64, K % 64 == 0). With ``h`` [M, r * k],
+    ``lora_b`` (k tensors [n_i, r]) and ``lora_off`` (their first output rows, multiples of 4):
+    rows of target i also get ``scaling * h[:, i r:(i + 1) r] @ lora_b[i].T`` in the epilogue."""
+    if _gpu(x):
+        if lora_b is None:
+            return _native.kernels().nf4_gemv(x, qweight, absmax, N, K)
+        return _native.kernels().nf4_gemv(x, qweight, absmax, N, K, h, list(lora_b), list(lora_off), scaling)
+    return _ref.nf4_gemv(x, qweight, absmax, N, K, h, lora_b, lora_off, scaling)

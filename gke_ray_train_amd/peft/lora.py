@@ -442,6 +442,7 @@ class LoraLinear(nn.Module):
         self._wk_order = None
         self._wk_key = None  # (order, B versions, optimizer generation) the tail was last built from
         self._bt = None     # [R, out]: the B blocks transposed (adapter-gradient kernel), with W'
+        self._acat = None   # (key, A_cat) of the decode branch when the A matrices are not adjacent
 
     @property
     def kcat_pad(self) -> int:
@@ -559,6 +560,47 @@ class LoraLinear(nn.Module):
             from ..ops.linear import transposed_weight
             transposed_weight(w)
 
+    def _decode_acat(self, As):
+        """(order, A_cat) for the decode branch: the ``_packed`` view when the adapters sit in a flat
+        buffer, else a concatenation kept while the A matrices are unchanged (keyed like ``_wk_key``:
+        data pointers, version counters, ``param_generation()``; decode runs without autograd)."""
+        pk = _packed(As)
+        if pk is not None:
+            return pk
+        key = (tuple((a.data_ptr(), a._version) for a in As), param_generation())
+        c = self._acat
+        if c is None or c[0] != key:
+            if As[0].is_cuda and torch.cuda.is_current_stream_capturing():  # not into a graph's pool
+                return list(range(len(As))), torch.cat([a.detach() for a in As], 0)
+            self._acat = c = (key, torch.cat([a.detach() for a in As], 0))
+        return list(range(len(As))), c[1]
+
+    def _decode_forward(self, x) -> Optional[torch.Tensor]:
+        """Decode step on an NF4 base (1-4 rows, no autograd, dropout inactive): h = gemv(x, A_cat),
+        then ONE GEMV from the codes whose epilogue adds every target's s * h_i B_i^T
+        (csrc/kernels/gemv_nf4.hip). None when it does not apply: the caller takes ``_LoraFn``."""
+        b = self.base
+        k = len(self.targets)
+        if not (isinstance(b, NF4Linear) and 1 <= k <= 4 and 8 <= self.r <= 64 and self.r % 8 == 0
+                and all(off % 4 == 0 for _, off, _ in self.targets)
+                and not (self.training and self.dropout_p > 0)):
+            return None
+        names = [t[0] for t in self.targets]
+        As = [self.lora_A[n] for n in names]
+        Bs = [self.lora_B[n] for n in names]
+        if not all(t.dtype == torch.bfloat16 and t.is_cuda and t.is_contiguous() for t in As + Bs):
+            return None
+        x2 = b.gemv_input(x)
+        if x2 is None:
+            return None
+        order, acat = self._decode_acat(As)
+        if acat.data_ptr() % 16 != 0:
+            return None
+        h = _native.kernels().gemv(x2, acat)                   # [rows, r * k], column block j = target order[j]
+        y = ops.nf4_gemv(x2, b.qweight, b._absmax_f32(), self.out_features, self.in_features, h,
+                         [Bs[i].detach() for i in order], [self._spec[i][0] for i in order], self.scaling)
+        return y.view(*x.shape[:-1], self.out_features)
+
     def direct_grad_params(self) -> List[nn.Parameter]:
         """Parameters whose gradient the GPU backward writes into the engine's slot itself."""
         return list(self.lora_A.values()) + list(self.lora_B.values())
@@ -569,6 +611,10 @@ class LoraLinear(nn.Module):
             seed, offset = ops.fused.dropout_seed_offset(x) if p > 0 else (0, 0)
             names = [t[0] for t in self.targets]
             R = self.r * len(names)
+            if not torch.is_grad_enabled():  # decode on an NF4 base (before the K-concatenated form:
+                y = self._decode_forward(x)  # a producer's tail columns are just a wider row stride)
+                if y is not None:
+                    return y
             if (getattr(x, "_grt_tail", 0) == R and R and x.dim() == 2 and x.stride(1) == 1
                     and x.stride(0) == self.in_features + R and self.kcat_pad == R):
                 ab = [self.lora_A[n] for n in names] + [self.lora_B[n] for n in names]

@@ -37,6 +37,19 @@ class BitsAndBytesConfig:
             raise ValueError("only nf4 is implemented")
 
 
+# Decode (1-4 rows, no autograd): multiply straight from the NF4 codes (csrc/kernels/gemv_nf4.hip)
+# instead of dequantising the projection for the library GEMM. GRT_NF4_GEMV=0: the dequantising path.
+_NF4_GEMV = os.environ.get("GRT_NF4_GEMV", "1") != "0"
+# Row limit of the NF4 GEMV: the kernel's own 4, with and without the dequant cache. Without the
+# cache the alternative re-dequantises the layer for every token (>= 8x the bytes at any row count).
+# With it the alternative is the library GEMM on the resident bf16 W: Llama-3.1-8B QLoRA r = 64 graph
+# decode, arms alternating in one process, batch 1 / 2 / 3 / 4: 314 / 536 / 572 / 699 tokens/s from
+# the codes against 118 / 234 / 347 / 464 (profiles/nf4_decode.md), so the kernel keeps every batch
+# it takes. GRT_NF4_GEMV_MAX_ROWS lowers the limit.
+NF4_GEMV_KERNEL_ROWS = 4
+NF4_GEMV_MAX_ROWS = min(int(os.environ.get("GRT_NF4_GEMV_MAX_ROWS", NF4_GEMV_KERNEL_ROWS)), NF4_GEMV_KERNEL_ROWS)
+
+
 class _NF4Matmul(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, layer):
@@ -98,6 +111,40 @@ class NF4Linear(nn.Module):
         codes = self.absmax_q.to(torch.float32) - 128.0
         sc = self.absmax_scale.repeat_interleave(256)[:nb]
         return codes / 127.0 * sc + self.absmax_offset
+
+    def _absmax_f32(self) -> torch.Tensor:
+        """Contiguous fp32 absmax for the NF4 GEMV, which takes no nested quantisation. A
+        ``double_quant`` layer expands its 8-bit absmax once and keeps the result (a plain attribute,
+        not a buffer: never saved) until the packed tensors change: 0.0625 bytes per parameter
+        resident on top of the codes. Under graph capture nothing is cached (the tensor would belong
+        to the graph's pool); the decoder's warm-up step runs first and fills the cache."""
+        if not self.double_quant:
+            return self.absmax
+        key = self._cache_key() + (self.absmax_q.data_ptr(), self.absmax_q._version, self.absmax_scale._version,
+                                   self.absmax_offset._version)
+        c = getattr(self, "_absmax_cache", None)
+        if c is not None and c[0] == key:
+            return c[1]
+        a = self._absmax().contiguous()
+        if not (a.is_cuda and torch.cuda.is_current_stream_capturing()):
+            self._absmax_cache = (key, a)
+        return a
+
+    def gemv_input(self, x: torch.Tensor) -> Optional[torch.Tensor]:
+        """``x`` as the [rows, in_features] view the NF4 GEMV takes, or None when the decode kernel
+        does not apply (autograd on, not the GPU / bf16 / blocksize-64 format, in_features % 64,
+        more rows than the limit, unaligned rows): the caller then takes the dequantising path."""
+        K = self.in_features
+        if not (_NF4_GEMV and not torch.is_grad_enabled() and x.is_cuda and self.qweight.is_cuda
+                and self.compute_dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and self.blocksize == 64
+                and K % 64 == 0 and x.shape[-1] == K and x.numel() > 0
+                and x.numel() // K <= NF4_GEMV_MAX_ROWS):
+            return None
+        x2 = x.reshape(-1, K)
+        if x2.stride(1) != 1 or x2.stride(0) % 8 != 0 or x2.stride(0) < K or x2.data_ptr() % 16 != 0 \
+                or self.qweight.data_ptr() % 16 != 0:
+            return None
+        return x2
 
     def _dequant(self) -> torch.Tensor:
         n = self.in_features * self.out_features
@@ -172,6 +219,10 @@ class NF4Linear(nn.Module):
             x = x.to(self.compute_dtype)
         if torch.is_grad_enabled() and x.requires_grad:
             return _NF4Matmul.apply(x, self)
+        x2 = self.gemv_input(x)
+        if x2 is not None:  # decode: 1-4 rows straight from the codes
+            y = ops.nf4_gemv(x2, self.qweight, self._absmax_f32(), self.out_features, self.in_features)
+            return y.view(*x.shape[:-1], self.out_features)
         return F.linear(x, self.dequantize())
 
 

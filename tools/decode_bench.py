@@ -1,7 +1,12 @@
 """Decode throughput on MI355X: eager cached decode vs the HIP-graph decoder (models/generation.py).
 Llama-3.1-8B architecture, random init, bf16, batch 1, prompt 512, 128 new tokens (the
 reference's inference comparison generates up to MAX_NEW_GENERATION_TOKENS_INFERENCE = 300
-tokens per sample, ray-jobs/fine_tune_config.json:35). One JSON line per mode."""
+tokens per sample, ray-jobs/fine_tune_config.json:35). One JSON line per mode.
+
+``DECODE_QUANT=nf4`` (optionally ``DECODE_LORA=<r>``: LoRA on all 7 targets, non-zero lora_B) times
+HIP-graph decode from a 4-bit base instead: the NF4 GEMV (csrc/kernels/gemv_nf4.hip) against the dequantising path it replaces, with the dequant cache
+on and off, the arms alternating ``DECODE_ROUNDS`` (2) times in this one process. ``DECODE_CACHE=0|1``
+keeps one cache mode (70B: 0); ``DECODE_B`` may be a comma list here."""
 import json
 import os
 import sys
@@ -12,9 +17,64 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gke_ray_train_amd.models import build_llama  # noqa: E402
 
+QUANT = os.environ.get("DECODE_QUANT", "")
 model = sys.argv[1] if len(sys.argv) > 1 else "llama3.1-8b"
+B_ENV = os.environ.get("DECODE_B", "1")  # sequences decoded together (batch of requests)
+
+
+def nf4_main():
+    from gke_ray_train_amd.peft import BitsAndBytesConfig, LoraConfig, get_peft_model, quantize_model_
+    from gke_ray_train_amd.peft import quant
+    if QUANT != "nf4":
+        sys.exit("DECODE_QUANT: only nf4")
+    r = int(os.environ.get("DECODE_LORA", "0"))
+    new = int(os.environ.get("DECODE_NEW", "128"))
+    net = build_llama(model, device="cuda", dtype=torch.bfloat16, seed=0)
+    cfg = net.config
+    quantize_model_(net, BitsAndBytesConfig())
+    net = get_peft_model(net, LoraConfig(r=r, lora_alpha=16)) if r else net
+    if r:
+        for lw in net.lora_modules.values():
+            for p in lw.lora_B.values():
+                p.data.normal_(0, 0.02)
+    net.eval()
+    base = net.base_model if r else net
+    caches = [c for c in ("1", "0") if os.environ.get("DECODE_CACHE", c) == c]
+    for B in [int(b) for b in B_ENV.split(",")]:  # here DECODE_B may be a list: one model build for all
+        ids = torch.randint(0, cfg.vocab_size, (B, 512), device="cuda")
+        nf4_arms(net, base, quant, ids, B, r, new, caches)
+
+
+def nf4_arms(net, base, quant, ids, B, r, new, caches):
+    for rnd in range(int(os.environ.get("DECODE_ROUNDS", "2"))):
+        for cache in caches:
+            for kern in (False, True):
+                quant.set_dequant_cache(base, cache)
+                quant._NF4_GEMV = kern
+                net.generate(ids, max_new_tokens=8, use_graph=True)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                net.generate(ids, max_new_tokens=2, use_graph=True)  # prefill, capture and one replay
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                out = net.generate(ids, max_new_tokens=new, use_graph=True)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t1
+                step = (dt - (t1 - t0)) / (new - 2)  # seconds per replayed step
+                print(json.dumps({"model": model, "quant": "nf4", "lora_r": r, "dequant_cache": cache == "1",
+                                  "nf4_gemv": kern, "batch": B, "round": rnd, "new_tokens": out.shape[1] - 512,
+                                  "seconds": round(dt, 3),
+                                  "tokens_per_s": round(B * (out.shape[1] - 512) / dt, 1),
+                                  "decode_step_ms": round(step * 1e3, 3),
+                                  "decode_tokens_per_s": round(B / step, 1)}), flush=True)
+        torch.cuda.empty_cache()
+
+
+if QUANT:
+    nf4_main()
+    sys.exit(0)
+B = int(B_ENV)
 m = build_llama(model, device="cuda", dtype=torch.bfloat16, seed=0)
-B = int(os.environ.get("DECODE_B", "1"))  # sequences decoded together (batch of requests)
 ids = torch.randint(0, m.config.vocab_size, (B, 512), device="cuda")
 from gke_ray_train_amd.ops import linear as _lin  # noqa: E402
 

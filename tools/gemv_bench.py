@@ -7,6 +7,10 @@ the projections that produce the residual stream, the residual-add + rstd epilog
 per shape.
 
     python tools/gemv_bench.py [--m 1] [--reps 50] [--flush]
+
+``--nf4``: the NF4 GEMV (csrc/kernels/gemv_nf4.hip) on the four quantised projection shapes instead,
+plain and with the r = 64 LoRA epilogue on every sub-projection, as effective TB/s of code bytes
+(N x K / 2 / time), next to the bf16 GEMV and the library GEMM on the dequantised weight.
 """
 import argparse
 import json
@@ -45,16 +49,51 @@ def med(fn, reps):
     return statistics.median(ts)
 
 
+# (N, K, [(offset, rows) of each LoRA target])
+NF4_SHAPES = {"qkv": (6144, 4096, [(0, 4096), (4096, 1024), (5120, 1024)]), "o": (4096, 4096, [(0, 4096)]),
+              "gate_up": (28672, 4096, [(0, 14336), (14336, 14336)]), "down": (4096, 14336, [(0, 4096)])}
+
+
+def nf4_main(a):
+    C = _native.kernels()
+    dev = torch.device("cuda")
+    r = 64
+    tot = tot_lora = 0.0
+    for name, (N, K, spans) in NF4_SHAPES.items():
+        w = torch.randn(N, K, device=dev, dtype=torch.bfloat16)
+        q, am = ops.nf4_quantize(w.view(-1), 64)
+        x = torch.randn(a.m, K, device=dev, dtype=torch.bfloat16)
+        h = torch.randn(a.m, r * len(spans), device=dev, dtype=torch.bfloat16)
+        Bs = [torch.randn(n, r, device=dev, dtype=torch.bfloat16) * 0.05 for _, n in spans]
+        offs = [o for o, _ in spans]
+        us = med(lambda: C.nf4_gemv(x, q, am, N, K), a.reps)
+        lus = med(lambda: C.nf4_gemv(x, q, am, N, K, h, Bs, offs, 0.25), a.reps)
+        bf = med(lambda: C.gemv(x, w), a.reps)
+        lib = med(lambda: torch.nn.functional.linear(x, w), a.reps)
+        nb = N * K // 2
+        tot += us * 32
+        tot_lora += lus * 32
+        print(json.dumps({"shape": name, "N": N, "K": K, "m": a.m, "nf4_gemv_us": round(us, 1),
+                          "nf4_gemv_TBps_of_codes": round(nb / us / 1e6, 2), "nf4_gemv_lora_r64_us": round(lus, 1),
+                          "bf16_gemv_us": round(bf, 1), "library_us": round(lib, 1)}), flush=True)
+        del w, q, am
+    print(json.dumps({"nf4_projections_per_token_ms": round(tot / 1e3, 3),
+                      "with_lora_epilogue_ms": round(tot_lora / 1e3, 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--m", type=int, default=1)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--flush", action="store_true",
                     help="evict the weights between calls (the decode step reads 16 GB between two uses)")
+    ap.add_argument("--nf4", action="store_true", help="the NF4 GEMV on the quantised projection shapes")
     a = ap.parse_args()
     global FLUSH
     if a.flush:
         FLUSH = torch.ones(2 ** 28, device="cuda")
+    if a.nf4:
+        return nf4_main(a)
     C = _native.kernels()
     dev = torch.device("cuda")
     ws = torch.zeros(C.sumsq_blocks(), device=dev)
