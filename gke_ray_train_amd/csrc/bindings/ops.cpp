@@ -1296,6 +1296,93 @@ Tensor gemv_fused(const Tensor& x, const Tensor& w, const Tensor& sumsq, int64_t
   return y;
 }
 
+// One token per row of logits [B, V] (sample.hip): greedy argmax, or (do_sample) a Gumbel-max draw
+// from softmax(logits / temperature) cut to top_k (0: off) and then top_p (1.0: off), with the
+// noise of (seed, counter[0], row, index). Returns tokens [B] int64 (next_ids itself when given).
+// keep_mask [B, V] uint8: debug output of the kept set. The state tensors (finished, finish_step,
+// step, out; with them optionally next_ids, eos_ids, pad_id) add the generate() bookkeeping:
+// finished rows emit pad_id, the token goes to next_ids[b] and out[b, step[0]], and a row whose
+// winner is one of eos_ids gets finished[b] = true, finish_step[b] = step[0]. max_steps: the caller's
+// bound on step[0] + 1 (a step past out's last column writes no column).
+Tensor sample_logits(const Tensor& logits, bool do_sample, double temperature, int64_t top_k, double top_p, int64_t seed,
+                     const optional<Tensor>& counter, const optional<Tensor>& keep_mask,
+                     const optional<Tensor>& finished, const optional<Tensor>& finish_step,
+                     const optional<Tensor>& step, const optional<Tensor>& next_ids, const optional<Tensor>& out,
+                     const optional<Tensor>& eos_ids, const optional<int64_t>& pad_id, int64_t max_steps) {
+  check_cuda(logits, "logits");
+  const grt::DType dt = dtype_of(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1, "sample_logits: logits [B, V], B, V >= 1");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V <= INT32_MAX && B <= INT32_MAX, "sample_logits: B, V < 2^31");
+  TORCH_CHECK(logits.stride(1) == 1 && (B == 1 || logits.stride(0) >= V),
+              "sample_logits: last dimension contiguous, row stride >= V");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % logits.element_size() == 0, "sample_logits: alignment");
+  TORCH_CHECK(temperature > 0.0 && std::isfinite(temperature), "sample_logits: temperature must be > 0, got ", temperature);
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "sample_logits: top_p must be in (0, 1], got ", top_p);
+  TORCH_CHECK(top_k >= 0, "sample_logits: top_k must be >= 0, got ", top_k);
+  auto state_vec = [&](const optional<Tensor>& t, const char* name, int64_t n) -> int64_t* {
+    check_contig(*t, name);
+    TORCH_CHECK(t->scalar_type() == at::kLong && t->numel() == n && t->device() == logits.device(), "sample_logits: ", name,
+                " must be int64 with ", n, " element(s) on the logits' device");
+    return t->data_ptr<int64_t>();
+  };
+  grt::SampleArgs a{};
+  a.B = (int)B, a.V = (int)V, a.ld = B == 1 ? V : logits.stride(0);
+  a.do_sample = do_sample, a.inv_t = 1.0f / (float)temperature;
+  a.top_k = (int)std::min<int64_t>(top_k, V), a.top_p = top_p, a.seed = seed;
+  int lg = 0;
+  while ((int64_t(1) << lg) < V) ++lg;
+  a.mass_scale = std::ldexp(1.0f, std::min(40, 62 - lg));
+  if (counter.has_value() && counter->defined()) a.counter = state_vec(counter, "counter", 1);
+  if (keep_mask.has_value() && keep_mask->defined()) {
+    TORCH_CHECK(do_sample, "sample_logits: keep_mask is an output of the sampling mode");
+    check_contig(*keep_mask, "keep_mask");
+    TORCH_CHECK(keep_mask->scalar_type() == at::kByte && keep_mask->dim() == 2 && keep_mask->size(0) == B &&
+                    keep_mask->size(1) == V && keep_mask->device() == logits.device(),
+                "sample_logits: keep_mask uint8 [B, V] on the logits' device");
+    a.keep_mask = keep_mask->data_ptr<uint8_t>();
+  }
+  const bool state = finished.has_value() && finished->defined();
+  auto given = [](const optional<Tensor>& t) { return t.has_value() && t->defined(); };
+  TORCH_CHECK(state == given(finish_step) && state == given(step) && state == given(out),
+              "sample_logits: finished, finish_step, step and out come together");
+  TORCH_CHECK(state || (!given(eos_ids) && !pad_id.has_value()), "sample_logits: eos_ids / pad_id need the state tensors");
+  c10::OptionalDeviceGuard dg(logits.device());
+  Tensor tokens;
+  if (given(next_ids)) {
+    state_vec(next_ids, "next_ids", B);
+    tokens = *next_ids;
+  } else {
+    tokens = at::empty({B}, logits.options().dtype(at::kLong));
+  }
+  a.tokens = tokens.data_ptr<int64_t>();
+  if (state) {
+    check_contig(*finished, "finished");
+    TORCH_CHECK((finished->scalar_type() == at::kBool || finished->scalar_type() == at::kByte) && finished->numel() == B &&
+                    finished->device() == logits.device(),
+                "sample_logits: finished bool / uint8 [B] on the logits' device");
+    a.finished = static_cast<uint8_t*>(finished->data_ptr());
+    a.finish_step = state_vec(finish_step, "finish_step", B);
+    a.step = state_vec(step, "step", 1);
+    check_cuda(*out, "out");
+    TORCH_CHECK(out->scalar_type() == at::kLong && out->dim() == 2 && out->size(0) == B && out->size(1) >= 1 &&
+                    out->stride(1) == 1 && (B == 1 || out->stride(0) >= out->size(1)) && out->device() == logits.device(),
+                "sample_logits: out int64 [B, >= 1], last dimension contiguous, on the logits' device");
+    // step[0] lives on the device: the caller states its bound and out must hold that many columns
+    TORCH_CHECK(max_steps >= 1 && out->size(1) >= max_steps, "sample_logits: out has ", out->size(1),
+                " columns, too narrow for max_steps = ", max_steps);
+    a.out = out->data_ptr<int64_t>(), a.out_ld = B == 1 ? out->size(1) : out->stride(0), a.out_cols = out->size(1);
+    if (given(eos_ids)) {
+      TORCH_CHECK(eos_ids->numel() <= grt::kSampleMaxEos, "sample_logits: at most ", grt::kSampleMaxEos, " EOS ids, got ",
+                  eos_ids->numel());
+      a.eos = state_vec(eos_ids, "eos_ids", eos_ids->numel()), a.n_eos = (int)eos_ids->numel();
+    }
+    a.has_pad = pad_id.has_value(), a.pad_id = pad_id.value_or(0);
+  }
+  grt::sample_logits(logits.data_ptr(), dt, a, cur_stream(logits));
+  return tokens;
+}
+
 // y [M, N] = x W^T straight from the NF4 codes of W [N, K] (gemv_nf4.hip; blocksize 64, fp32 absmax),
 // 1-4 rows. With h [M, r * targets], lora_b (target i: bf16 [n_i, r]) and lora_off (its first output
 // row): rows of target i also get scaling * h[:, i r : (i + 1) r] lora_b[i]^T.
@@ -1674,6 +1761,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nf4_gemv", &nf4_gemv, py::arg("x"), py::arg("qweight"), py::arg("absmax"), py::arg("N"), py::arg("K"),
         py::arg("h") = py::none(), py::arg("lora_b") = py::none(), py::arg("lora_off") = py::none(),
         py::arg("scaling") = 1.0);
+  m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("do_sample") = false, py::arg("temperature") = 1.0,
+        py::arg("top_k") = 0, py::arg("top_p") = 1.0, py::arg("seed") = 0, py::arg("counter") = py::none(),
+        py::arg("keep_mask") = py::none(), py::arg("finished") = py::none(), py::arg("finish_step") = py::none(),
+        py::arg("step") = py::none(), py::arg("next_ids") = py::none(), py::arg("out") = py::none(),
+        py::arg("eos_ids") = py::none(), py::arg("pad_id") = py::none(), py::arg("max_steps") = 1);
   m.def("attn_decode", &attn_decode);
   m.def("attn_decode_d64", &attn_decode_d64);
   m.def("attn_decode_d64_partials", &attn_decode_d64_partials,

@@ -407,6 +407,38 @@ struct Nf4Gemv {
 };
 void gemv_nf4(const Nf4Gemv& f, hipStream_t s);
 
+// ---------------- token sampler (sample.hip) ----------------
+// One token per row of logits [B, V] (bf16 / fp32, row stride ld elements): greedy argmax, or a
+// Gumbel-max draw over the top-k / top-p kept set of logits * inv_t (semantics and the noise
+// recipe: sample.hip header). tokens [B] always gets the result. finished != null adds the
+// generate() bookkeeping for row b at step n = step[0]: tok = finished[b] && has_pad ? pad_id :
+// winner -> tokens[b] and out[b][n] (if n < out_cols); a winner among eos[0 .. n_eos) on an
+// unfinished row sets finished[b] = 1 and finish_step[b] = n.
+constexpr int kSampleMaxEos = 8;
+struct SampleArgs {
+  int B, V;
+  int64_t ld;
+  bool do_sample;
+  float inv_t;
+  int top_k;          // 0 or >= V: off
+  double top_p;       // 1.0: off
+  float mass_scale;   // 2^s, s = min(40, 62 - ceil(log2 V)): V fixed-point masses fit 64 bits
+  int64_t seed;
+  const int64_t* counter;  // device; null: 0
+  uint8_t* keep_mask;      // [B, V] or null (sampling only)
+  int64_t* tokens;
+  uint8_t* finished;
+  int64_t* finish_step;
+  const int64_t* step;
+  const int64_t* eos;  // device, n_eos <= kSampleMaxEos ids
+  int n_eos;
+  bool has_pad;
+  int64_t pad_id;
+  int64_t* out;
+  int64_t out_ld, out_cols;
+};
+void sample_logits(const void* logits, DType dt, const SampleArgs& a, hipStream_t s);
+
 // ---------------- xGMI peer-to-peer collectives (ipc_comm.hip) ----------------
 constexpr int kIpcMaxRanks = 8;
 constexpr int kIpcMaxBlocks = 64;

@@ -10,17 +10,26 @@ absolute positions by the RoPE kernel's position array.
 
 On MI355X the one-token decode step is launch-bound (≈10 kernels per layer, a few µs of work
 each), so ``GraphDecoder`` captures the WHOLE step — embedding, every layer, final norm, LM head
-and the greedy argmax — into one HIP graph and replays it per token. Everything that changes
-between tokens lives in device tensors the graph reads: the current position (RoPE position
-array and the KV-cache write index) and the per-row valid key length, which the flash kernel
-takes as its padding mask (``seqlens_k``) over the full-length cache, so the kernel's tile loop
-still covers only the keys written so far. EOS checks touch the host every ``sync_every``
-tokens instead of every token; the output is trimmed to HF's stopping point.
+and, when it is given a ``SamplerConfig``, the choice of the token — into one HIP graph and replays
+it per token. Everything that changes between tokens lives in device tensors the graph reads: the
+current position (RoPE position array and the KV-cache write index) and the per-row valid key
+length, which the flash kernel takes as its padding mask (``seqlens_k``) over the full-length
+cache, so the kernel's tile loop still covers only the keys written so far.
+
+With a sampler the step ends in ``sample_logits`` (csrc/kernels/sample.hip): greedy argmax or a
+temperature / top-k / top-p draw with counter-based noise, plus the loop's bookkeeping (pad after
+EOS, finished flags, the next step's input id, the output column), so ``generate()`` is
+back-to-back replays with no torch op between them and one host read of ``finished.all()`` every
+``sync_every`` tokens; the output is trimmed to HF's stopping point. ``GRT_DEVICE_SAMPLER=0`` (or
+``device_loop=False``) restores the host loop, which picks the token with torch ops on the logits
+the graph returns. ``ops/_ref.py::sample_tokens`` is the sampler's host implementation: the same
+logits, seed and counter give the same token on either device.
 """
 from __future__ import annotations
 
 import os
-from typing import List, Optional, Union
+from dataclasses import dataclass
+from typing import List, Optional, Tuple, Union
 
 import torch
 
@@ -189,14 +198,39 @@ def _fused_norm_layer_step(layer, h, first: bool, ws: _NormWorkspace, B, cos, si
     return K.gemv_fused(gu, mlp.down_proj.weight, ws.sumsq, 1, swiglu=True, res=h)
 
 
+_DEVICE_SAMPLER = os.environ.get("GRT_DEVICE_SAMPLER", "1") != "0"
+SAMPLER_MAX_EOS = 8  # kSampleMaxEos (csrc/include/grt_kernels.h)
+
+
+@dataclass
+class SamplerConfig:
+    """What the device sampler at the end of a captured decode step does (``sample_logits``)."""
+    max_new_tokens: int
+    do_sample: bool = False
+    temperature: float = 1.0
+    top_k: int = 0          # 0: off
+    top_p: float = 1.0      # 1.0: off
+    seed: int = 0
+    eos_ids: Tuple[int, ...] = ()
+    pad_id: Optional[int] = None
+
+
 class GraphDecoder:
-    """Greedy / sampling decode with the per-token step captured in a HIP graph (see module doc).
+    """One-token decode step captured in a HIP graph (see module doc).
 
-    Usage: ``dec = GraphDecoder(model, B, max_len)``; ``logits = dec.prefill(ids)`` (eager, any
-    prompt length); then ``logits = dec.step(next_ids)`` per token (graph replay). Needs a bf16
-    Llama on the GPU with head_dim 128 or 64 (the HIP RoPE epilogue / decode attention kernels)."""
+    Without a sampler the step returns logits and the caller picks the token: ``dec =
+    GraphDecoder(model, B, max_len)``; ``logits = dec.prefill(ids)`` (eager, any prompt length);
+    then ``logits = dec.step(next_ids)`` per token (graph replay).
 
-    def __init__(self, model, B: int, max_len: int):
+    With ``sampler=SamplerConfig(...)`` the captured step ends in the device sampler, which also
+    feeds the next step: ``dec.first_token(dec.prefill(ids))`` picks token 0 with the same op,
+    eagerly, then ``dec.advance()`` per token is nothing but a graph replay. Tokens land in
+    ``dec.out[:, n]``, ``dec.finished`` / ``dec.finish_step`` hold the EOS state.
+
+    Needs a bf16 Llama on the GPU with head_dim 128 or 64 (the HIP RoPE epilogue / decode
+    attention kernels)."""
+
+    def __init__(self, model, B: int, max_len: int, sampler: Optional[SamplerConfig] = None):
         self.model = model
         p = next(model.parameters())
         self.device = p.device
@@ -213,6 +247,40 @@ class GraphDecoder:
         # residual adds / norms inside the GEMVs when every projection is a plain bf16 Linear
         self.norm_ws = (_NormWorkspace(B, self.device)
                         if self.device.type == "cuda" and _norm_fusable(model, B) else None)
+        self.sampler = sampler
+        if sampler is not None:
+            if len(sampler.eos_ids) > SAMPLER_MAX_EOS:
+                raise ValueError(f"the device sampler takes at most {SAMPLER_MAX_EOS} EOS ids, got {len(sampler.eos_ids)}")
+            if sampler.max_new_tokens < 1:
+                raise ValueError("SamplerConfig.max_new_tokens must be >= 1")
+            dev = self.device
+            self.finished = torch.zeros(B, dtype=torch.bool, device=dev)
+            self.finish_step = torch.full((B,), -1, dtype=torch.long, device=dev)
+            self.n_step = torch.zeros(1, dtype=torch.long, device=dev)    # column of `out` the next token takes
+            self.counter = torch.zeros(1, dtype=torch.long, device=dev)   # noise counter: one per token
+            self.out = torch.zeros(B, sampler.max_new_tokens, dtype=torch.long, device=dev)
+            self.eos_t = (torch.tensor(sorted(sampler.eos_ids), dtype=torch.long, device=dev)
+                          if sampler.eos_ids else None)
+
+    def _sample(self, logits: torch.Tensor) -> None:
+        """Pick one token per row with the device sampler and do the loop's bookkeeping: the token
+        goes to ``ids`` (the next step's embedding input) and ``out[:, n_step]``; then both
+        counters move on. All of it device work on the current stream (graph-capturable)."""
+        c = self.sampler
+        if logits.dtype not in (torch.bfloat16, torch.float32):
+            logits = logits.float()
+        _native.kernels().sample_logits(
+            logits, do_sample=c.do_sample, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p, seed=c.seed,
+            counter=self.counter, finished=self.finished, finish_step=self.finish_step, step=self.n_step,
+            next_ids=self.ids.view(self.B), out=self.out, eos_ids=self.eos_t, pad_id=c.pad_id,
+            max_steps=c.max_new_tokens)
+        self.counter.add_(1)
+        self.n_step.add_(1)
+
+    @torch.no_grad()
+    def first_token(self, logits: torch.Tensor) -> None:
+        """Token 0 from the prefill logits: the captured step's sampler call, run eagerly."""
+        self._sample(logits)
 
     @torch.no_grad()
     def prefill(self, input_ids: torch.Tensor) -> torch.Tensor:
@@ -233,17 +301,22 @@ class GraphDecoder:
                                            self.cache, li, self.pos_b, self.lens)
             fn = m.model.norm
             logits = _native.kernels().gemv_fused(h, m.lm_head.weight, self.norm_ws.sumsq, 1, g=fn.weight,
-                                                  eps=fn.eps).float()
-            self.pos_b.add_(1)
-            self.pos_l.add_(1)
-            self.lens.add_(1)
-            return logits
+                                                  eps=fn.eps)
+            return self._step_tail(logits)
         residual = None
         for li, layer in enumerate(m.model.layers):
             h, residual = _graph_layer_step(layer, h, residual, self.B, self.cos, self.sin, self.cache, li,
                                             self.pos_b, self.pos_l, self.lens)
         x, _ = ops.add_rms_norm(h, residual, m.model.norm.weight, m.model.norm.eps)
-        logits = m.lm_head(x).float()
+        return self._step_tail(m.lm_head(x))
+
+    def _step_tail(self, logits):
+        """End of the step: the sampler reads the LM head's bf16 logits as they are; without one
+        the caller gets an fp32 copy. Then the positions move on."""
+        if self.sampler is not None:
+            self._sample(logits)
+        else:
+            logits = logits.float()
         self.pos_b.add_(1)
         self.pos_l.add_(1)
         self.lens.add_(1)
@@ -253,22 +326,41 @@ class GraphDecoder:
         # warm up on a side stream (allocator pools, library handles), then capture one step;
         # the warm-up step's cache writes land at the current position and are rewritten by the
         # first replay, and the position tensors are restored afterwards
-        saved = (self.pos_b.clone(), self.pos_l.clone(), self.lens.clone())
+        state = [self.pos_b, self.pos_l, self.lens]
+        if self.sampler is not None:  # the sampler's epilogue writes these; column n_step of `out`
+            # is written again, with the same token, by the first replay
+            state += [self.ids, self.finished, self.finish_step, self.n_step, self.counter]
+        saved = [t.clone() for t in state]
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
             self._step_body()
         torch.cuda.current_stream(self.device).wait_stream(s)
-        for t, v in zip((self.pos_b, self.pos_l, self.lens), saved):
+        for t, v in zip(state, saved):
             t.copy_(v)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.logits = self._step_body()
-        for t, v in zip((self.pos_b, self.pos_l, self.lens), saved):
+        for t, v in zip(state, saved):
             t.copy_(v)
 
     @torch.no_grad()
+    def advance(self) -> None:
+        """One more token on the device: a graph replay and nothing else (needs a sampler; the
+        previous token is already in ``ids``)."""
+        if self.sampler is None:
+            raise RuntimeError("GraphDecoder.advance() needs a SamplerConfig; use step(next_ids)")
+        if self.cache.len >= self.cache.max_len:
+            raise RuntimeError("KV cache full")
+        if self.graph is None:
+            self._capture()
+        self.graph.replay()
+        self.cache.len += 1
+
+    @torch.no_grad()
     def step(self, next_ids: torch.Tensor) -> torch.Tensor:
+        if self.sampler is not None:
+            raise RuntimeError("GraphDecoder.step() returns logits; with a SamplerConfig use advance()")
         if self.cache.len >= self.cache.max_len:
             raise RuntimeError("KV cache full")
         self.ids.copy_(next_ids.view(self.B, 1))
@@ -286,24 +378,74 @@ def _graph_ok(model, input_ids) -> bool:
             and _native.kernels_available())
 
 
+def _device_loop_ok(graph: bool, generator, n_eos: int, max_new_tokens: int) -> bool:
+    return (graph and generator is None and n_eos <= SAMPLER_MAX_EOS and max_new_tokens >= 1
+            and _native.kernels_available())
+
+
 @torch.no_grad()
 def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              eos_token_id: Optional[Union[int, List[int]]] = None, do_sample: bool = False, temperature: float = 1.0,
              top_p: Optional[float] = None, attention_mask=None, pad_token_id=None, generator=None,
-             use_graph: Optional[bool] = None, sync_every: int = 16, **_):
+             use_graph: Optional[bool] = None, sync_every: int = 16, top_k: Optional[int] = None,
+             seed: Optional[int] = None, device_loop: Optional[bool] = None, **_):
     """Returns [B, prompt + generated] token ids (HF ``generate`` output convention).
 
     A bf16 model on the GPU with head_dim 128 or 64 (``llama3.2-1b``) decodes through the HIP-graph
     decoder by default (fused RoPE epilogue of the qkv GEMV, split-K decode attention at either
     width). ``use_graph=False`` gives the eager step; ``GRT_DECODE_ATTN=0`` sends the one-token
     attention to the flash forward kernel with ``seqlens_k`` and ``GRT_GEMV_NORM=0`` keeps the
-    norms and ``rope_append`` outside the GEMVs."""
+    norms and ``rope_append`` outside the GEMVs.
+
+    Sampling (``do_sample=True``): ``temperature``, then ``top_k`` (None / 0: off; ties at the
+    k-th value are all kept), then ``top_p`` over the renormalised survivors, as HF chains them.
+    Without a ``generator`` the draw is a Gumbel-max over counter-based noise of (``seed``, token
+    number, row, vocabulary index): the same ``seed`` and the same logits give the same tokens on
+    the GPU and on the CPU. ``seed=None`` draws one from torch's default generator, so
+    ``torch.manual_seed`` governs it. With a ``generator`` the draw is ``torch.multinomial``'s.
+
+    On the graph path with no ``generator`` and at most 8 EOS ids, the token is picked inside the
+    captured step by the device sampler (``device_loop``, default on; ``GRT_DEVICE_SAMPLER=0`` or
+    ``device_loop=False`` restore the host loop): the loop is graph replays and one host read of
+    ``finished.all()`` every ``sync_every`` tokens."""
     was = model.training
     model.eval()
     B, S = input_ids.shape
     eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
     eos_t = torch.tensor(sorted(eos), device=input_ids.device) if eos else None
     graph = use_graph if use_graph is not None else _graph_ok(model, input_ids)
+    temperature = max(temperature, 1e-5)
+    top_k = int(top_k) if top_k else 0
+    top_p = 1.0 if top_p is None else float(top_p)
+    if top_k < 0 or not 0.0 < top_p <= 1.0:
+        raise ValueError(f"generate: top_k must be >= 0 and top_p in (0, 1], got top_k={top_k}, top_p={top_p}")
+    if do_sample and generator is None and seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # torch's default generator: torch.manual_seed governs
+    seed = int(seed or 0)
+    can = _device_loop_ok(graph, generator, len(eos), max_new_tokens)
+    if device_loop and not can:
+        raise ValueError("generate: device_loop=True needs the graph path (bf16 model on the GPU, native kernels), "
+                         f"no generator, at most {SAMPLER_MAX_EOS} EOS ids and max_new_tokens >= 1")
+    if can and (device_loop if device_loop is not None else _DEVICE_SAMPLER):
+        cfg = SamplerConfig(max_new_tokens=max_new_tokens, do_sample=do_sample, temperature=temperature, top_k=top_k,
+                            top_p=top_p, seed=seed, eos_ids=tuple(sorted(eos)), pad_id=pad_token_id)
+        dec = GraphDecoder(model, B, S + max_new_tokens, sampler=cfg)
+        dec.first_token(dec.prefill(input_ids))
+        done = 1
+        while done < max_new_tokens:
+            # replays up to the next multiple of sync_every tokens, then one host read
+            for _i in range(min(sync_every - done % sync_every, max_new_tokens - done)):
+                dec.advance()
+                done += 1
+            if eos and done % sync_every == 0 and bool(dec.finished.all()):
+                break
+        if eos:  # HF stops right after the token that finished the last row
+            last = dec.finish_step.tolist()
+            if min(last) >= 0:
+                done = max(last) + 1
+        if was:
+            model.train()
+        return torch.cat([input_ids, dec.out[:, :done]], 1)
     if graph:
         dec = GraphDecoder(model, B, S + max_new_tokens)
         logits = dec.prefill(input_ids)
@@ -320,9 +462,16 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
     all_done = []  # device flags: every row finished after token t
     for t in range(max_new_tokens):
-        if do_sample:
-            probs = torch.softmax(logits / max(temperature, 1e-5), -1)
-            if top_p is not None and top_p < 1.0:
+        if do_sample and generator is None:
+            # the device sampler's host implementation: token t draws the noise of counter t
+            nxt = _ref.sample_tokens(logits, seed=seed, counter=t, temperature=temperature, top_k=top_k, top_p=top_p)
+        elif do_sample:
+            probs = torch.softmax(logits / temperature, -1)
+            if 0 < top_k < probs.shape[-1]:
+                kth = probs.topk(top_k, -1).values[..., -1:]
+                probs = torch.where(probs < kth, torch.zeros_like(probs), probs)
+                probs = probs / probs.sum(-1, keepdim=True)
+            if top_p < 1.0:
                 sp, si = probs.sort(-1, descending=True)
                 keep = sp.cumsum(-1) - sp <= top_p
                 sp = sp * keep

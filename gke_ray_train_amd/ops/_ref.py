@@ -118,6 +118,98 @@ def dropout_keep_mask(seed: int, offset: int, n: int, p: float) -> torch.Tensor:
     return torch.from_numpy(bits >= np.uint64(thr))
 
 
+_M64 = (1 << 64) - 1
+
+
+def _s64(x: int) -> int:
+    """Python int -> the int64 with the same low 64 bits (torch has no uint64 arithmetic)."""
+    x &= _M64
+    return x - (1 << 64) if x >> 63 else x
+
+
+def _lsr(x, s: int):
+    return (x >> s) & ((1 << (64 - s)) - 1)  # logical shift of an int64 tensor / a masked python int
+
+
+def _splitmix64_any(x):
+    """hash_u64 (grt_common.h) on a python int (masked to 64 bits) or on an int64 tensor, whose
+    wrapping two's-complement arithmetic gives the same bits as the kernel's uint64."""
+    if isinstance(x, int):
+        x = (x + 0x9E3779B97F4A7C15) & _M64
+        x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+        x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+        return x ^ (x >> 31)
+    x = x + _s64(0x9E3779B97F4A7C15)
+    x = (x ^ _lsr(x, 30)) * _s64(0xBF58476D1CE4E5B9)
+    x = (x ^ _lsr(x, 27)) * _s64(0x94D049BB133111EB)
+    return x ^ _lsr(x, 31)
+
+
+def sample_noise(seed: int, counter: int, B: int, V: int, device=None) -> torch.Tensor:
+    """[B, V] float64 Gumbel noise of the sampler (csrc/kernels/sample.hip), the same bits:
+        key = splitmix64(splitmix64(seed) + counter)            (64-bit wrapping add)
+        h_i = splitmix64(key ^ ((row << 32) | i))               (i < 2^31)
+        n_i = h_i >> 41 (the top 23 bits), u_i = (n_i + 0.5) * 2^-23, g_i = -log(-log(u_i))
+    u_i is exact in fp32; the kernel takes the two logs in fp32, this takes them in float64."""
+    key = _splitmix64_any((_splitmix64_any(seed & _M64) + counter) & _M64)
+    row = torch.arange(B, device=device, dtype=torch.int64)[:, None] << 32
+    idx = row | torch.arange(V, device=device, dtype=torch.int64)[None, :]
+    n = _lsr(_splitmix64_any(idx ^ _s64(key)), 41)
+    u = (n.double() + 0.5) * 2.0 ** -23
+    return -torch.log(-torch.log(u))
+
+
+def sample_filter(logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+    """The sampler's kept set, in float64 on z = fp32(logits) * fp32(1 / temperature) (the one
+    fp32 multiply the kernel does; NaN counts as -inf). Returns (z [B, V] float64, keep [B, V] bool,
+    frac [B, V] float64 = M_>(i) / Z, the top-p coordinate of every top-k survivor, inf elsewhere).
+    top-k (0 or >= V: off) keeps i iff #{j : z_j > z_i} < k; top-p (1.0: off) keeps a survivor iff
+    M_>(i) < top_p * Z, with e_j = exp(z_j - z_max), Z the survivors' sum and M_>(i) their sum over
+    z_j > z_i. Ties stay or go together, the maximum always stays, -inf never does."""
+    B, V = logits.shape
+    inv_t = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(temperature), dtype=torch.float32)
+    z = (logits.float() * inv_t.to(logits.device)).double()
+    z = torch.where(torch.isnan(z), torch.full_like(z, -math.inf), z)
+    asc, order = z.sort(-1)
+    n_le = torch.searchsorted(asc, z, right=True)  # #{j : z_j <= z_i}
+    keep = z > -math.inf
+    if 0 < top_k < V:
+        keep &= (V - n_le) < top_k
+    zmax = asc[:, -1:]
+    finite_max = torch.where(torch.isfinite(zmax), zmax, torch.zeros_like(zmax))
+    e = torch.where(keep, torch.exp(z - finite_max), torch.zeros_like(z))
+    e = torch.where(keep & (z == zmax), torch.ones_like(e), e)  # +inf rows: the maxima carry the mass
+    Z = e.sum(-1, keepdim=True)
+    # mass of the survivors with z_j <= z_i: a prefix sum in ascending order, read at n_le - 1
+    e_asc = torch.gather(e, -1, order)
+    m_le = torch.gather(e_asc.cumsum(-1), -1, (n_le - 1).clamp_(min=0))
+    frac = torch.where(keep, ((Z - m_le) / Z).clamp_(min=0.0), torch.full_like(z, math.inf))
+    frac = torch.where(keep & (z == zmax), torch.zeros_like(frac), frac)  # exactly 0 for the maximum
+    if top_p < 1.0:
+        keep = keep & (frac < top_p)
+    return z, keep, frac
+
+
+def sample_tokens(logits, seed: int = 0, counter: int = 0, temperature: float = 1.0, top_k: int = 0,
+                  top_p: float = 1.0, do_sample: bool = True) -> torch.Tensor:
+    """Host implementation (and oracle) of the device sampler: one token per row of logits [B, V],
+    int64 [B] on the logits' device. Greedy: argmax of the raw logits. Sampling: Gumbel-max,
+    argmax over the kept set (``sample_filter``) of z_i + g_i with ``sample_noise(seed, counter)``.
+    Lowest index on ties; index 0 when nothing is kept. The same (seed, counter) and the same
+    logits give the same tokens as the kernel (up to fp32-vs-float64 near-ties)."""
+    B, V = logits.shape
+    if do_sample:
+        z, keep, _ = sample_filter(logits, temperature, top_k or 0, 1.0 if top_p is None else top_p)
+        score = torch.where(keep, z + sample_noise(seed, counter, B, V, logits.device), torch.full_like(z, -math.inf))
+    else:
+        score = logits.double()
+        score = torch.where(torch.isnan(score), torch.full_like(score, -math.inf), score)
+    best = score.max(-1, keepdim=True).values
+    idx = torch.arange(V, device=logits.device).expand(B, V)
+    tok = torch.where(score == best, idx, torch.full_like(idx, V)).min(-1).values
+    return torch.where(best.squeeze(-1) == -math.inf, torch.zeros_like(tok), tok)
+
+
 def attention(q, k, v, causal=True, scale=None, seqlens_k=None, dropout_p=0.0, seed=0):
     """q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] -> o [B,Sq,Hq,D]; math in fp32 (explicit matmul/softmax —
     no SDPA backend dispatch). ``dropout_p`` drops attention probabilities with the kernel's mask."""

@@ -6,7 +6,10 @@ tokens per sample, ray-jobs/fine_tune_config.json:35). One JSON line per mode.
 ``DECODE_QUANT=nf4`` (optionally ``DECODE_LORA=<r>``: LoRA on all 7 targets, non-zero lora_B) times
 HIP-graph decode from a 4-bit base instead: the NF4 GEMV (csrc/kernels/gemv_nf4.hip) against the dequantising path it replaces, with the dequant cache
 on and off, the arms alternating ``DECODE_ROUNDS`` (2) times in this one process. ``DECODE_CACHE=0|1``
-keeps one cache mode (70B: 0); ``DECODE_B`` may be a comma list here."""
+keeps one cache mode (70B: 0); ``DECODE_B`` may be a comma list here.
+
+``DECODE_SAMPLE=greedy|top_p`` and / or ``DECODE_DEVICE_LOOP=0|1`` times the HIP-graph decoder with the
+token picked on the device inside the captured step against the host loop (``sampler_main``)."""
 import json
 import os
 import sys
@@ -70,8 +73,43 @@ def nf4_arms(net, base, quant, ids, B, r, new, caches):
         torch.cuda.empty_cache()
 
 
+def sampler_main():
+    """``DECODE_SAMPLE=greedy|top_p`` and / or ``DECODE_DEVICE_LOOP=0|1``: HIP-graph decode with the
+    token picked by the device sampler inside the captured step (device loop) against the host loop
+    on the graph's logits. ``top_p``: do_sample, top_p 0.9, seed 0. Unset ``DECODE_DEVICE_LOOP`` runs
+    both loops, alternating, ``DECODE_ROUNDS`` (3) times in this one process; ``DECODE_NEW`` tokens."""
+    sample = os.environ.get("DECODE_SAMPLE", "greedy")
+    if sample not in ("greedy", "top_p"):
+        sys.exit("DECODE_SAMPLE: greedy or top_p")
+    loops = [bool(int(v)) for v in os.environ.get("DECODE_DEVICE_LOOP", "0,1").split(",")]
+    new = int(os.environ.get("DECODE_NEW", "128"))
+    B = int(B_ENV)
+    net = build_llama(model, device="cuda", dtype=torch.bfloat16, seed=0).eval()
+    ids = torch.randint(0, net.config.vocab_size, (B, 512), device="cuda")
+    kw = dict(do_sample=True, top_p=0.9, seed=0) if sample == "top_p" else {}
+    for rnd in range(int(os.environ.get("DECODE_ROUNDS", "3"))):
+        for loop in loops:
+            net.generate(ids, max_new_tokens=8, use_graph=True, device_loop=loop, **kw)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            net.generate(ids, max_new_tokens=2, use_graph=True, device_loop=loop, **kw)  # prefill, capture, one replay
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            out = net.generate(ids, max_new_tokens=new, use_graph=True, device_loop=loop, **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t1
+            step = (dt - (t1 - t0)) / (new - 2)  # seconds per token after the first two
+            print(json.dumps({"model": model, "sample": sample, "device_loop": loop, "batch": B, "round": rnd,
+                              "new_tokens": out.shape[1] - 512, "seconds": round(dt, 3),
+                              "tokens_per_s": round(B * (out.shape[1] - 512) / dt, 1),
+                              "ms_per_token": round(step * 1e3, 3)}), flush=True)
+
+
 if QUANT:
     nf4_main()
+    sys.exit(0)
+if "DECODE_SAMPLE" in os.environ or "DECODE_DEVICE_LOOP" in os.environ:
+    sampler_main()
     sys.exit(0)
 B = int(B_ENV)
 m = build_llama(model, device="cuda", dtype=torch.bfloat16, seed=0)
