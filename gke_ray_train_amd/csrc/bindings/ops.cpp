@@ -711,6 +711,72 @@ void adamw(Tensor& p, const Tensor& gr, Tensor& m, Tensor& v, const optional<Ten
                   gscale.has_value() ? gscale->data_ptr<float>() : nullptr, cur_stream(p), (int)max_blocks,
                   index_offset);
 }
+// 8-bit block-quantised moments (adamw8.hip): uint8 codes [n] and fp32 absmax [ceil(n / 256)]. The
+// kernels load 8 codes at a time, so code arrays are 8-byte aligned.
+void check_q8_state(const Tensor& codes, const Tensor& absmax, const Tensor& on, int64_t n, const char* what) {
+  check_contig(codes, what);
+  check_contig(absmax, what);
+  TORCH_CHECK(codes.scalar_type() == at::kByte && codes.numel() == n, what, ": codes must be uint8 [", n, "], got ",
+              codes.numel(), " of ", codes.scalar_type());
+  TORCH_CHECK(absmax.scalar_type() == at::kFloat && absmax.numel() == (n + 255) / 256, what,
+              ": absmax must be fp32 [ceil(n / 256) = ", (n + 255) / 256, "], got ", absmax.numel(), " of ",
+              absmax.scalar_type());
+  check_optim_device(codes, on, what, "p");
+  check_optim_device(absmax, on, what, "p");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(codes.data_ptr()) % 8 == 0, what, ": codes must be 8-byte aligned");
+}
+void adamw8(Tensor& p, const Tensor& gr, Tensor& codes_m, Tensor& absmax_m, Tensor& codes_v, Tensor& absmax_v,
+            const optional<Tensor>& master, const Tensor& hyper, const optional<Tensor>& gscale, int64_t max_blocks,
+            int64_t index_offset) {
+  TORCH_CHECK(index_offset >= 0 && index_offset % 256 == 0,
+              "adamw8: index_offset must be a multiple of 256 (a slice starts on a block boundary), got ", index_offset);
+  check_contig(p, "p");
+  check_contig(gr, "g");
+  const int64_t n = p.numel();
+  TORCH_CHECK(gr.numel() == n, "adamw8 size mismatch: p ", n, ", g ", gr.numel());
+  const bool bf = p.scalar_type() == at::kBFloat16 && gr.scalar_type() == at::kBFloat16;
+  const bool f32 = p.scalar_type() == at::kFloat && gr.scalar_type() == at::kFloat;
+  TORCH_CHECK(bf || f32, "adamw8: p and g must both be bf16 or both be fp32, got ", p.scalar_type(), " and ",
+              gr.scalar_type());
+  check_optim_device(gr, p, "adamw8: g", "p");
+  check_q8_state(codes_m, absmax_m, p, n, "adamw8: exp_avg");
+  check_q8_state(codes_v, absmax_v, p, n, "adamw8: exp_avg_sq");
+  check_optim_f32(hyper, p, 10, kHyperDoc, "p");
+  if (gscale.has_value()) check_optim_f32(*gscale, p, 2, "adamw8: gscale ([norm, coefficient])", "p");
+  for (const Tensor* t : std::initializer_list<const Tensor*>{&p, &gr})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0 ||
+                    (t->element_size() == 2 && reinterpret_cast<uintptr_t>(t->data_ptr()) % 8 == 0),
+                "adamw8 operands must be vector aligned");
+  if (master.has_value()) {
+    check_contig(*master, "master");
+    TORCH_CHECK(bf, "adamw8: a master copy goes with bf16 parameters");
+    TORCH_CHECK(master->numel() == n && master->scalar_type() == at::kFloat, "master fp32 [n]");
+    check_optim_device(*master, p, "adamw8: master", "p");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(master->data_ptr()) % 16 == 0, "adamw8: master must be 16-byte aligned");
+  }
+  c10::OptionalDeviceGuard g(p.device());
+  grt::adamw8_step(dtype_of(p), p.data_ptr(), gr.data_ptr(), codes_m.data_ptr<uint8_t>(), absmax_m.data_ptr<float>(),
+                   codes_v.data_ptr<uint8_t>(), absmax_v.data_ptr<float>(),
+                   master.has_value() ? master->data_ptr<float>() : nullptr, n, hyper.data_ptr<float>(),
+                   gscale.has_value() ? gscale->data_ptr<float>() : nullptr, cur_stream(p), (int)max_blocks,
+                   index_offset);
+}
+void quantize_blockwise8(const Tensor& x, Tensor& codes, Tensor& absmax, bool is_signed) {
+  check_contig(x, "x");
+  TORCH_CHECK(x.scalar_type() == at::kFloat, "quantize_blockwise8: x must be fp32, got ", x.scalar_type());
+  check_q8_state(codes, absmax, x, x.numel(), "quantize_blockwise8");
+  c10::OptionalDeviceGuard g(x.device());
+  grt::quantize_blockwise8(x.data_ptr<float>(), codes.data_ptr<uint8_t>(), absmax.data_ptr<float>(), x.numel(),
+                           is_signed, cur_stream(x));
+}
+void dequantize_blockwise8(const Tensor& codes, const Tensor& absmax, Tensor& out, bool is_signed) {
+  check_contig(out, "out");
+  TORCH_CHECK(out.scalar_type() == at::kFloat, "dequantize_blockwise8: out must be fp32, got ", out.scalar_type());
+  check_q8_state(codes, absmax, out, out.numel(), "dequantize_blockwise8");
+  c10::OptionalDeviceGuard g(out.device());
+  grt::dequantize_blockwise8(codes.data_ptr<uint8_t>(), absmax.data_ptr<float>(), out.data_ptr<float>(), out.numel(),
+                             is_signed, cur_stream(out));
+}
 // AdamW on a bf16 weight [rows, cols] that also writes pt = W^T [cols, rows] (see optim.hip)
 void adamw_t(Tensor& p, const Tensor& gr, Tensor& m, Tensor& v, const Tensor& hyper, const optional<Tensor>& gscale,
              Tensor& pt, int64_t index_offset) {
@@ -1713,6 +1779,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw", &adamw, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("master"),
         py::arg("hyper"), py::arg("gscale"), py::arg("max_blocks") = 0, py::arg("index_offset") = 0);
   m.def("adamw_t", &adamw_t);
+  m.def("adamw8", &adamw8, py::arg("p"), py::arg("g"), py::arg("codes_m"), py::arg("absmax_m"), py::arg("codes_v"),
+        py::arg("absmax_v"), py::arg("master"), py::arg("hyper"), py::arg("gscale"), py::arg("max_blocks") = 0,
+        py::arg("index_offset") = 0);
+  m.def("quantize_blockwise8", &quantize_blockwise8, py::arg("x"), py::arg("codes"), py::arg("absmax"),
+        py::arg("signed"));
+  m.def("dequantize_blockwise8", &dequantize_blockwise8, py::arg("codes"), py::arg("absmax"), py::arg("out"),
+        py::arg("signed"));
   m.def("scale_", &scale_);
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("scale"),
         py::arg("causal"), py::arg("seqlens_k"), py::arg("dropout_p") = 0.0, py::arg("seed") = 0,

@@ -99,6 +99,17 @@ void adamw_step(DType pdt, DType gdt, void* p, const void* g, float* m, float* v
 // that also writes its transpose pt [cols][rows]; ioff = flat index of p[0] (stochastic rounding).
 void adamw_t_step(void* p, const void* g, float* m, float* v, void* pt, int64_t rows, int64_t cols,
                   const float* hyper, const float* grad_scale_ptr, hipStream_t s, int64_t ioff);
+// AdamW with 8-bit block-quantised moments (adamw8.hip): blocks of 256 elements counted from p[0],
+// uint8 codes [n] (8-byte aligned) and fp32 absmax [ceil(n / 256)] per moment, updated in place.
+// dt: p and g alike (bf16, master optional; fp32, no master). hyper, grad_scale_ptr, max_blocks as in
+// adamw_step; index_offset (a multiple of 256) = flat element index of p[0] (stochastic rounding).
+void adamw8_step(DType dt, void* p, const void* g, uint8_t* codes_m, float* absmax_m, uint8_t* codes_v,
+                 float* absmax_v, float* master, int64_t n, const float* hyper, const float* grad_scale_ptr,
+                 hipStream_t s, int max_blocks = 0, int64_t index_offset = 0);
+// The same quantiser standalone (is_signed: the exp_avg table, otherwise the exp_avg_sq table).
+void quantize_blockwise8(const float* x, uint8_t* codes, float* absmax, int64_t n, bool is_signed, hipStream_t s);
+void dequantize_blockwise8(const uint8_t* codes, const float* absmax, float* out, int64_t n, bool is_signed,
+                           hipStream_t s);
 // Scale in place: x *= a (device scalar pointer or host value when a_ptr == null).
 void scale_inplace(DType dt, void* x, int64_t n, float a, const float* a_ptr, hipStream_t s);
 

@@ -298,3 +298,90 @@ def nf4_gemv(x, packed, absmax, N, K, h=None, lora_b=None, lora_off=None, scalin
         for i, (b, off) in enumerate(zip(lora_b, lora_off)):
             y[:, off:off + b.shape[0]] += scaling * (h[:, i * r:(i + 1) * r].double() @ b.double().t())
     return y.to(x.dtype)
+
+
+# ----------------------------------------------------------------------------- 8-bit block-quantised moments
+# The "dynamic" 8-bit type of the 8-bit-optimizers paper (Dettmers et al., 2021): decades 10^-6 ..
+# 10^0, a linear fraction inside each decade (bin centres of [0.1, 1]), and twice as many fraction
+# steps in every higher decade. A state tensor is cut into blocks of 256 consecutive elements, each
+# with one fp32 absmax; an element is the uint8 code of the table entry nearest to x / absmax. The
+# tables here are this project's own (the kernels in adamw8.hip build the same ones from the same
+# formula); they are not bitsandbytes' tables.
+Q8_BLOCK = 256
+_Q8_DECADES = (1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1, 1.0)
+
+
+def _q8_magnitudes(first_steps):
+    """first_steps fraction steps in the decade of 10^-6, doubling per decade; float64, increasing."""
+    out = []
+    for i, d in enumerate(_Q8_DECADES):
+        k = first_steps << i
+        out.extend(d * (0.1 + 0.9 * (j + 0.5) / k) for j in range(k))
+    return out
+
+
+def _q8_tables():
+    mag = _q8_magnitudes(1)  # 127 magnitudes; mirrored, with 0 and +-1, they would make 257 entries:
+    # the smallest negative magnitude (-5.5e-7) is the one left out, so all 256 codes are in use
+    signed = [-1.0] + [-x for x in reversed(mag[1:])] + [0.0] + mag + [1.0]
+    unsigned = [0.0] + _q8_magnitudes(2) + [1.0]  # 254 magnitudes
+    out = []
+    for t in (signed, unsigned):
+        assert len(t) == 256
+        t32 = torch.tensor(t, dtype=torch.float64).to(torch.float32)
+        mids = ((t32[1:].double() + t32[:-1].double()) / 2).to(torch.float32)
+        out.append((t32, mids))
+    return out
+
+
+(Q8_SIGNED, _Q8_SIGNED_MIDS), (Q8_UNSIGNED, _Q8_UNSIGNED_MIDS) = _q8_tables()
+Q8_ZERO_CODE = {True: int((Q8_SIGNED == 0).nonzero()), False: int((Q8_UNSIGNED == 0).nonzero())}  # 127, 0
+
+
+def q8_table(signed: bool) -> torch.Tensor:
+    """The 256 fp32 entries, increasing: signed for exp_avg, unsigned for exp_avg_sq."""
+    return Q8_SIGNED if signed else Q8_UNSIGNED
+
+
+def q8_blocks(n: int) -> int:
+    return (n + Q8_BLOCK - 1) // Q8_BLOCK
+
+
+def quantize_blockwise8(x, signed: bool):
+    """x (any shape, read flat) -> (uint8 codes [n], fp32 absmax [ceil(n / 256)]). The code is the
+    number of table midpoints below fp32(x / absmax), i.e. the nearest entry (the lower one at a
+    tie); a block with absmax == 0 stores the code of 0.0. A non-finite element makes its block's
+    absmax non-finite."""
+    flat = x.detach().reshape(-1).to(torch.float32)
+    n = flat.numel()
+    nb = q8_blocks(n)
+    blocks = torch.zeros(nb * Q8_BLOCK, dtype=torch.float32, device=flat.device)
+    blocks[:n] = flat
+    blocks = blocks.view(nb, Q8_BLOCK)
+    absmax = blocks.abs().amax(dim=1)  # NaN propagates
+    normed = torch.where(absmax[:, None] == 0, torch.zeros_like(blocks), blocks / absmax[:, None])
+    mids = (_Q8_SIGNED_MIDS if signed else _Q8_UNSIGNED_MIDS).to(flat.device)
+    codes = torch.bucketize(normed, mids, right=False)  # mids[c - 1] < x <= mids[c]
+    codes = torch.where(normed.isnan(), torch.zeros_like(codes), codes)  # no midpoint is below NaN
+    return codes.view(-1)[:n].to(torch.uint8), absmax
+
+
+def dequantize_blockwise8(codes, absmax, signed: bool):
+    """fp32(table[code] * absmax of the element's block), flat [n]."""
+    n = codes.numel()
+    table = q8_table(signed).to(codes.device)
+    scale = absmax.to(torch.float32).repeat_interleave(Q8_BLOCK)[:n]
+    return table[codes.reshape(-1).long()] * scale
+
+
+def adamw8_(p, g, codes_m, absmax_m, codes_v, absmax_v, step, lr, beta1, beta2, eps, wd, grad_scale=1.0,
+            master=None):
+    """adamw_ on the dequantised moments: the parameter is computed from the fp32 new moments, which
+    are quantised and stored (in place) only afterwards."""
+    m = dequantize_blockwise8(codes_m, absmax_m, True).view(p.shape)
+    v = dequantize_blockwise8(codes_v, absmax_v, False).view(p.shape)
+    adamw_(p, g, m, v, step, lr, beta1, beta2, eps, wd, grad_scale=grad_scale, master=master)
+    for x, codes, absmax, signed in ((m, codes_m, absmax_m, True), (v, codes_v, absmax_v, False)):
+        c, a = quantize_blockwise8(x, signed)
+        codes.copy_(c)
+        absmax.copy_(a)

@@ -241,20 +241,33 @@ class FusedAdamW(torch.optim.Optimizer):
                 st = self._init_state(p)
                 st["step"] += 1
                 step = float(st["step"].item()) if st["step"].device.type == "cpu" else float(st["step"])
-                bc1 = 1.0 - b1 ** step
-                bc2 = 1.0 - b2 ** step
-                master = st.get("master")
-                if p.is_cuda:
-                    hb = self._hyper_buf(p.device, (gi,))
-                    upload_hyper(hb, [lr, b1, b2, eps, wd, bc1, bc2, 1.0, self._sr(), step])
-                    g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                    _native.kernels().adamw(p.data, g, st["exp_avg"], st["exp_avg_sq"], master, hb,
-                                            None if grad_scale is None else grad_scale.buf)
-                else:
-                    gs = 1.0 if grad_scale is None else float(grad_scale.buf[1])
-                    _ref.adamw_(p.data, p.grad, st["exp_avg"], st["exp_avg_sq"], step, lr, b1, b2, eps, wd,
-                                grad_scale=gs, master=master)
+                self._update(p, st, gi, (lr, b1, b2, eps, wd), step, grad_scale)
         return loss
+
+    def _update(self, p, st, gi, hp, step, grad_scale):
+        """One parameter's update from its gradient: the HIP kernel on the GPU, ops/_ref.py on the CPU."""
+        lr, b1, b2, eps, wd = hp
+        master = st.get("master")
+        if p.is_cuda:
+            hb = self._hyper_buf(p.device, (gi,))
+            upload_hyper(hb, [lr, b1, b2, eps, wd, 1.0 - b1 ** step, 1.0 - b2 ** step, 1.0, self._sr(), step])
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            _native.kernels().adamw(p.data, g, st["exp_avg"], st["exp_avg_sq"], master, hb,
+                                    None if grad_scale is None else grad_scale.buf)
+        else:
+            gs = 1.0 if grad_scale is None else float(grad_scale.buf[1])
+            _ref.adamw_(p.data, p.grad, st["exp_avg"], st["exp_avg_sq"], step, lr, b1, b2, eps, wd,
+                        grad_scale=gs, master=master)
+
+    # The data-parallel engine's portable optimizer state (parallel/ddp.py) reads and writes the flat
+    # moments of a flat parameter through these two, whatever form the optimizer keeps them in.
+    def flat_state_fp32(self, p, key: str) -> Optional[torch.Tensor]:
+        """State ``key`` (exp_avg / exp_avg_sq / master) of ``p`` as an fp32 tensor, or None."""
+        v = self.state.get(p, {}).get(key)
+        return v if isinstance(v, torch.Tensor) else None
+
+    def set_flat_state_fp32(self, p, key: str, value: torch.Tensor) -> None:
+        self.state[p][key] = self._state_tensor(value, p)
 
 
 class OffloadedAdamW(FusedAdamW):
@@ -353,6 +366,129 @@ class OffloadedAdamW(FusedAdamW):
         comp.wait_stream(up)
 
 
+class AdamW8bit(FusedAdamW):
+    """AdamW with 8-bit block-quantised moments (the role of bitsandbytes' 8-bit AdamW; HF ``optim``
+    names ``adamw_8bit`` / ``adamw_bnb_8bit`` / ``paged_adamw_8bit``, paging being unnecessary here).
+
+    Per parameter of at least ``min_8bit_size`` elements (bitsandbytes' rule; smaller tensors keep
+    fp32 moments and the ``adamw`` kernel): ``exp_avg_q`` / ``exp_avg_sq_q`` (uint8 codes, n) and
+    ``exp_avg_absmax`` / ``exp_avg_sq_absmax`` (fp32, one per block of 256 elements): about 2.03
+    bytes of state per element instead of 8. The scheme is ops/_ref.py's (this project's own tables,
+    not bitsandbytes'). GPU parameters are updated by the ``adamw8`` kernel in one pass, CPU
+    parameters by ``_ref.adamw8_``.
+
+    ``state_dict()`` has the ``torch.optim.AdamW`` layout (fp32 ``exp_avg`` / ``exp_avg_sq`` in the
+    parameter's shape, dequantised) and ``load_state_dict()`` quantises, so checkpoints move between
+    the 32-bit and the 8-bit optimizer in both directions; requantising dequantised moments gives
+    the same codes, so an 8-bit run resumed on the same layout continues bit for bit.
+    """
+
+    _Q8 = {"exp_avg": ("exp_avg_q", "exp_avg_absmax", True), "exp_avg_sq": ("exp_avg_sq_q", "exp_avg_sq_absmax", False)}
+
+    def __init__(self, params, min_8bit_size: int = 4096, **kw):
+        super().__init__(params, **kw)
+        self.min_8bit_size = int(min_8bit_size)
+
+    def _is_8bit(self, p) -> bool:
+        return p.numel() >= self.min_8bit_size
+
+    def _quantize(self, x: torch.Tensor, p: torch.Tensor, signed: bool):
+        x = x.detach().to(p.device, torch.float32).reshape(-1).contiguous()
+        if not p.is_cuda:
+            return _ref.quantize_blockwise8(x, signed)
+        codes = torch.empty(x.numel(), dtype=torch.uint8, device=p.device)
+        absmax = torch.empty(_ref.q8_blocks(x.numel()), dtype=torch.float32, device=p.device)
+        _native.kernels().quantize_blockwise8(x, codes, absmax, signed)
+        return codes, absmax
+
+    def _dequantize(self, st, key: str) -> torch.Tensor:
+        qk, ak, signed = self._Q8[key]
+        codes, absmax = st[qk], st[ak]
+        if not codes.is_cuda:
+            return _ref.dequantize_blockwise8(codes, absmax, signed)
+        out = torch.empty(codes.numel(), dtype=torch.float32, device=codes.device)
+        _native.kernels().dequantize_blockwise8(codes, absmax, out, signed)
+        return out
+
+    def _set_quantized(self, st, key: str, x: torch.Tensor, p: torch.Tensor) -> None:
+        qk, ak, signed = self._Q8[key]
+        st[qk], st[ak] = self._quantize(x, p, signed)
+        st.pop(key, None)
+
+    def _init_state(self, p):
+        if not self._is_8bit(p):
+            return super()._init_state(p)
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = torch.tensor(0.0)
+            n = p.numel()
+            for qk, ak, signed in self._Q8.values():  # fresh state: the code of 0.0, absmax 0
+                st[qk] = torch.full((n,), _ref.Q8_ZERO_CODE[signed], dtype=torch.uint8, device=p.device)
+                st[ak] = torch.zeros(_ref.q8_blocks(n), dtype=torch.float32, device=p.device)
+            if self.master_weights and p.dtype != torch.float32:
+                st["master"] = p.detach().float().contiguous()
+        return st
+
+    def prepare_gpu_step(self):
+        raise RuntimeError("AdamW8bit has no per-slice launch interface (the overlapped optimizer runs on "
+                           "FusedAdamW only); call step()")
+
+    def _update(self, p, st, gi, hp, step, grad_scale):
+        if "exp_avg_q" not in st:
+            return super()._update(p, st, gi, hp, step, grad_scale)
+        lr, b1, b2, eps, wd = hp
+        master = st.get("master")
+        q = (st["exp_avg_q"], st["exp_avg_absmax"], st["exp_avg_sq_q"], st["exp_avg_sq_absmax"])
+        if p.is_cuda:
+            hb = self._hyper_buf(p.device, (gi,))
+            upload_hyper(hb, [lr, b1, b2, eps, wd, 1.0 - b1 ** step, 1.0 - b2 ** step, 1.0, self._sr(), step])
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            _native.kernels().adamw8(p.data, g, *q, master, hb, None if grad_scale is None else grad_scale.buf)
+        else:
+            gs = 1.0 if grad_scale is None else float(grad_scale.buf[1])
+            _ref.adamw8_(p.data, p.grad, *q, step, lr, b1, b2, eps, wd, grad_scale=gs, master=master)
+
+    def state_dict(self):
+        sd = super().state_dict()
+        params = [p for g in self.param_groups for p in g["params"]]  # the order of the packed ids
+        state = {}
+        for pid, st in sd["state"].items():
+            out = {k: v for k, v in st.items() if not k.endswith(("_q", "_absmax"))}
+            if "exp_avg_q" in st:
+                for key in self._Q8:
+                    out[key] = self._dequantize(st, key).view(params[pid].shape)
+            state[pid] = out
+        sd["state"] = state
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)  # fp32 exp_avg / exp_avg_sq on the parameter's device
+        for g in self.param_groups:
+            for p in g["params"]:
+                st = self.state.get(p)
+                if st and self._is_8bit(p):
+                    for key in self._Q8:
+                        if isinstance(st.get(key), torch.Tensor):
+                            self._set_quantized(st, key, st[key], p)
+
+    def flat_state_fp32(self, p, key):
+        st = self.state.get(p, {})
+        if key in self._Q8 and self._Q8[key][0] in st:
+            return self._dequantize(st, key)
+        return super().flat_state_fp32(p, key)
+
+    def set_flat_state_fp32(self, p, key, value):
+        if key in self._Q8 and self._is_8bit(p):
+            self._set_quantized(self.state[p], key, value, p)
+        else:
+            super().set_flat_state_fp32(p, key, value)
+
+    def state_bytes(self) -> int:
+        """Bytes of optimizer state held (moments, absmax, master copies)."""
+        return sum(v.numel() * v.element_size() for st in self.state.values() for k, v in st.items()
+                   if isinstance(v, torch.Tensor) and k != "step")
+
+
 _EIGHT_BIT = ("paged_adamw_8bit", "adamw_8bit", "adamw_bnb_8bit", "paged_adamw8bit", "adamw8bit")
 
 
@@ -362,10 +498,23 @@ def make_optimizer(name: str, params, lr: float, weight_decay: float, betas=(0.9
     (OffloadedAdamW) — only worthwhile when HBM cannot hold them (e.g. 70B on one node)."""
     name = (name or "adamw_torch").lower()
     if name in _EIGHT_BIT:
-        # bitsandbytes' 8-bit AdamW keeps block-quantized moments: a different algorithm and memory
-        # footprint. Substituting 32-bit states silently would change both, so refuse loudly.
-        raise ValueError(f"optimizer {name!r} (8-bit block-quantized AdamW states) is not implemented; use "
-                         "'paged_adamw_32bit' / 'adamw_torch' (fp32 states, the reference config's choice)")
+        # 8-bit block-quantised moments are a different algorithm and memory footprint: where AdamW8bit
+        # cannot run on its kernels, refuse loudly; 32-bit states are never substituted.
+        params = list(params)
+        tensors = [t for g in params for t in (g["params"] if isinstance(g, dict) else [g])]
+        why = None
+        if offload:
+            why = "host-offloaded states are not implemented for it"
+        elif not tensors or not all(t.is_cuda for t in tensors):
+            why = "it runs on the GPU kernels and not every parameter is on a GPU"
+        elif not _native.kernels_available():
+            why = "the native kernels (_C.so) are not loaded"
+        if why is not None:
+            raise ValueError(f"optimizer {name!r} (8-bit block-quantized AdamW states) cannot be built: {why}. "
+                             "32-bit states are never substituted silently; ask for 'paged_adamw_32bit' / "
+                             "'adamw_torch' (fp32 states, the reference config's choice) instead")
+        return AdamW8bit(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                         master_weights=master_weights)
     if offload and name.startswith(("adamw", "paged_adamw", "fused_adamw")):
         return OffloadedAdamW(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
     if name in ("adamw", "adamw_torch", "adamw_hf", "adamw_32bit", "paged_adamw_32bit", "adamw_torch_fused",

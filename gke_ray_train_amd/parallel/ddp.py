@@ -626,7 +626,8 @@ class DistributedDataParallel(nn.Module):
 
     def portable_optimizer_state_dict(self, optimizer) -> Optional[dict]:
         """Collective. On rank 0: the optimizer state per model parameter (HF ``optimizer.pt``
-        layout, host tensors in the parameters' shapes); None on the other ranks."""
+        layout, host tensors in the parameters' shapes); None on the other ranks. The moments of an
+        ``AdamW8bit`` are written dequantised (fp32), so the file loads into either optimizer."""
         inner, fps = self._inner_opt(optimizer)
         named = self._named_trainable()
         index = {id(p): i for i, (_, p) in enumerate(named)}
@@ -636,8 +637,9 @@ class DistributedDataParallel(nn.Module):
             st = inner.state.get(fp, {})
             groups_out.append(dict({k: v for k, v in inner.param_groups[gi].items() if k != "params"},
                                    params=sorted(index[id(p)] for p in g.params)))
+            as_fp32 = getattr(inner, "flat_state_fp32", None)  # 8-bit moments come back dequantised
             for key in self._OPT_KEYS:
-                v = st.get(key)
+                v = as_fp32(fp, key) if as_fp32 is not None else st.get(key)
                 if not isinstance(v, torch.Tensor):
                     continue
                 full = self._gather_flat(g, v)
@@ -656,7 +658,13 @@ class DistributedDataParallel(nn.Module):
 
     def load_portable_optimizer_state_dict(self, optimizer, sd: dict):
         """Every rank: rebuild this engine's flat (or ZeRO shard) optimizer state from a
-        :meth:`portable_optimizer_state_dict` written at ANY world size / sharding."""
+        :meth:`portable_optimizer_state_dict` written at ANY world size / sharding.
+
+        ``AdamW8bit`` quantises the moments again in blocks of 256 elements of THIS engine's flat
+        (or shard) state. On the layout that wrote the file the blocks are the same and the codes
+        come back exactly; across a change of world size or sharding the blocks cut the parameters
+        elsewhere, each gets a new absmax, and the resumed moments are exact only to one
+        quantisation step (one table gap times the block's absmax)."""
         inner, fps = self._inner_opt(optimizer)
         named = self._named_trainable()
         names = [n for n, _ in named]
@@ -690,7 +698,7 @@ class DistributedDataParallel(nn.Module):
                         if a_ < e_:
                             src = sd["state"][index[id(p)]][key].reshape(-1)
                             out[base + a_ - lo:base + e_ - lo].copy_(src[a_ - o:e_ - o].float())
-                st[key] = inner._state_tensor(out, fp)
+                inner.set_flat_state_fp32(fp, key, out)  # AdamW8bit quantises the moments here
             if "step" in first:
                 st["step"] = torch.as_tensor(first["step"]).detach().to("cpu", torch.float32).clone().reshape(())
 
