@@ -37,16 +37,12 @@ __device__ __forceinline__ float adam_elem(float p, float gf, float& m, float& v
 // 16 random bits per element for stochastic rounding, 4 elements at a time (element base4 + k in
 // bits 16k .. 16k + 15), keyed by (step, flat element index): FAST = one 32-bit fmix per element
 // pair; otherwise one 64-bit splitmix per 4 elements.
-__device__ __forceinline__ uint32_t fmix32_o(uint32_t h) {
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
 template <bool FAST>
 __device__ __forceinline__ uint64_t sr_bits4(uint64_t srkey, uint64_t base4) {
   if constexpr (FAST) {
     const uint64_t pr = base4 >> 1;
     const uint32_t k = (uint32_t)srkey ^ ((uint32_t)(pr >> 32) * 0x9E3779B1u);
-    return (uint64_t)fmix32_o(k ^ (uint32_t)pr) | ((uint64_t)fmix32_o(k ^ (uint32_t)(pr + 1)) << 32);
+    return (uint64_t)fmix32(k ^ (uint32_t)pr) | ((uint64_t)fmix32(k ^ (uint32_t)(pr + 1)) << 32);
   } else {
     return hash_u64(srkey ^ (base4 >> 2));
   }

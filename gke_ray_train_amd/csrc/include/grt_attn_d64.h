@@ -3,6 +3,7 @@
 // per tile, a row-major and a transposed LDS image. Layout notes: header of attention_d64.hip.
 #pragma once
 #include "grt_common.h"
+#include "grt_mfma.h"
 
 namespace grt {
 namespace d64 {
@@ -18,22 +19,11 @@ static_assert(TK * (D / 8) == NT, "one 16-byte chunk per thread per tile");
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
 __device__ __forceinline__ bf16x8 zero8() {
   bf16x8 z;
 #pragma unroll
   for (int j = 0; j < 8; ++j) z[j] = static_cast<bf16>(0.f);
   return z;
-}
-__device__ __forceinline__ bf16x8 pack8(const f32x16& x, int base) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = static_cast<bf16>(x[base + j]);
-  return r;
 }
 
 // this thread's chunk of a 32-row tile: row tid & 31, columns 8 (tid >> 5) .. + 7
@@ -62,7 +52,7 @@ __device__ __forceinline__ void row_load(bf16x8 (&f)[4], const bf16* row, bool o
 __device__ __forceinline__ f32x16 rows_x_regs(const bf16* lds, const bf16x8 (&b)[4], f32x16 acc, int l32, int h) {
   const bf16* row = lds + l32 * LDR + h * 32;
 #pragma unroll
-  for (int s = 0; s < 4; ++s) acc = mfma(*reinterpret_cast<const bf16x8*>(row + 8 * s), b[s], acc);
+  for (int s = 0; s < 4; ++s) acc = mfma32(*reinterpret_cast<const bf16x8*>(row + 8 * s), b[s], acc);
   return acc;
 }
 
@@ -77,7 +67,7 @@ __device__ __forceinline__ void lds_t_x_acc(const bf16* ldt, const f32x16& pt, f
       const bf16* row = ldt + (db * 32 + l32) * LDT + 16 * s + 4 * h;
       const bf16x4 a0 = *reinterpret_cast<const bf16x4*>(row);
       const bf16x4 a1 = *reinterpret_cast<const bf16x4*>(row + 8);
-      out[db] = mfma(__builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7), b, out[db]);
+      out[db] = mfma32(__builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7), b, out[db]);
     }
   }
 }

@@ -39,62 +39,22 @@
 #include <type_traits>
 #include <utility>
 
+#include "grt_attn_dropout.h"
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_lds_image.h"
+#include "grt_mfma.h"
 
 namespace grt {
 namespace {
 
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+using namespace lds_image;  // swizzled image, transposed read, LDS-DMA (grt_lds_image.h)
 
 constexpr int D = 128;
 constexpr int kChunks = D / 8;  // 16-byte chunks per row
 
-__device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// byte offset of 16-byte chunk `ch` of row `row` in a [rows][128 x bf16] LDS image (T10 (b))
-__device__ __forceinline__ int img_off(int row, int ch) {
-  return row * 256 + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
 __device__ __forceinline__ bf16x8 lds_row_read(const char* base, int row, int ch) {
-  return *reinterpret_cast<const bf16x8*>(base + img_off(row, ch));
-}
-// transposed read: the 16-lane group reads rows r0..r0+3, columns c0..c0+15 (c0 multiple of 16);
-// lane i of the group receives column c0+i of the 4 rows.
-__device__ __forceinline__ bf16x4 lds_tr_read(const char* base, int r0, int c0, int lane16) {
-  const int q = lane16 >> 2, p = lane16 & 3;
-  const int col = c0 + 4 * p;
-  const char* a = base + img_off(r0 + q, col >> 3) + 8 * ((col >> 2) & 1);
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)a);
-}
-
-__device__ __forceinline__ bf16x8 cat(bf16x4 a, bf16x4 b) {
-  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-__device__ __forceinline__ bf16x8 pack8(const f32x16& x, int base) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = static_cast<bf16>(x[base + j]);
-  return r;
-}
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// Counter-based dropout hash (must match ops/_ref.attn_dropout_keep bit for bit): murmur3 fmix32
-// of the (batch*head, query, key) coordinates mixed with the per-call seed. Stateless, so the
-// forward and both backward kernels regenerate the same mask without storing it.
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-__device__ __forceinline__ uint32_t attn_dropout_hash(uint32_t seed, uint32_t bh, uint32_t q, uint32_t k) {
-  uint32_t h = seed ^ (bh * 0x9E3779B1u);
-  h = fmix32(h ^ (q * 0x85EBCA77u));
-  return fmix32(h ^ (k * 0xC2B2AE3Du));
-}
-__device__ __forceinline__ float drop_factor(const AttnParams& p, uint32_t bh, int q, int k) {
-  return attn_dropout_hash(p.drop_seed, bh, (uint32_t)q, (uint32_t)k) >= p.drop_thresh ? p.drop_scale : 0.f;
+  return *reinterpret_cast<const bf16x8*>(base + chunk_off(row, ch));
 }
 
 constexpr float kLog2e = 1.4426950408889634f;
@@ -113,17 +73,6 @@ __device__ __forceinline__ float halves_max(float x) {
 // between rescales the exponentiated scores are bounded by 2^kDeferLog2 (exact in fp32 l / O,
 // bf16 P keeps its relative precision).
 constexpr float kDeferLog2 = 8.f;
-
-// 16-byte LDS-DMA per lane to (wave-uniform LDS byte address) + lane * 16; M0 is written in the
-// same statement (compiler-reserved). Not tracked by hipcc's waitcnt pass: the kernel counts vmcnt.
-__device__ __forceinline__ void lds_dma16(const void* gptr, uint32_t lds_byte_addr) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-               :: "v"(gptr), "s"(lds_byte_addr) : "memory", "m0");
-}
-__device__ __forceinline__ uint32_t lds_u32(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)(p);
-}
-__device__ __forceinline__ int img_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
 // f(integral_constant<int, I>) for I in the sequence, unrolled at compile time (ring slots and
 // register-set parity stay compile-time constants in the pipelined loops)
@@ -231,10 +180,10 @@ __global__ __launch_bounds__(F3NT, 2) void attn_fwd_kernel(const AttnParams p) {
   if (p.causal) kend = min(kend, q0 + F3M + off);
   const int nt = kend > 0 ? (kend + F3N - 1) / F3N : 0;
 
-  const uint32_t smem0 = lds_u32(smem);
+  const uint32_t smem0 = lds_addr(smem);
   // wave w fills image rows 8w .. 8w+7 of K and V: two 1-KiB pieces of 4 rows per image
   const int row0 = 8 * w + g, row1 = row0 + 4;
-  const int ch0 = l16 ^ img_swz(row0), ch1 = l16 ^ img_swz(row1);
+  const int ch0 = l16 ^ swz(row0), ch1 = l16 ^ swz(row1);
   // per-lane source offsets of the two rows, fixed for the whole sweep: a tile inside the sequence
   // then costs one 64-bit add per DMA (the tile base is uniform, SALU); only the tile that crosses
   // the end takes the clamped per-lane row arithmetic (64-bit multiplies: quarter-rate VALU)
@@ -337,7 +286,7 @@ __global__ __launch_bounds__(F3NT, 2) void attn_fwd_kernel(const AttnParams p) {
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
         const int c0 = db * 32 + (g & 1) * 16;
-        va[stp][db] = cat(lds_tr_read(vi, kk, c0, l16), lds_tr_read(vi, kk + 8, c0, l16));
+        va[stp][db] = cat(tr_read(vi, kk, c0, l16), tr_read(vi, kk + 8, c0, l16));
       }
     }
 #pragma unroll
@@ -604,9 +553,9 @@ __global__ __launch_bounds__(K2NT, 1) void attn_bwd_dkdv_kernel(const AttnBwdPar
   // ---- LDS-DMA of tile j into a slot: wave w fills image rows 8w .. 8w+7 of Q and dO (two 1-KiB
   // pieces each; the XOR swizzle goes on the per-lane SOURCE chunk) and its own copy of the tile's
   // 32 lse2 and 32 delta values (lanes 0-7 / 8-15; lanes 16-63 repeat them).
-  const uint32_t smem0 = lds_u32(smem);
+  const uint32_t smem0 = lds_addr(smem);
   const int row0 = 8 * w + g, row1 = row0 + 4;
-  const int ch0 = l16 ^ img_swz(row0), ch1 = l16 ^ img_swz(row1);
+  const int ch0 = l16 ^ swz(row0), ch1 = l16 ^ swz(row1);
   const int sl = l16 & 7;
   const int64_t st_lane = (l16 < 8 ? (int64_t)p.B * p.Hq * Sqp : 0) + 4 * sl;  // lse2 | delta
   const uint32_t qo0 = (uint32_t)(row0 * p.q_ss + ch0 * 8), qo1 = (uint32_t)(row1 * p.q_ss + ch1 * 8);
@@ -734,8 +683,8 @@ __global__ __launch_bounds__(K2NT, 1) void attn_bwd_dkdv_kernel(const AttnBwdPar
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
         const int c0 = db * 32 + (g & 1) * 16;
-        oa[stp][db] = cat(lds_tr_read(qi + K2IMG, kk, c0, l16), lds_tr_read(qi + K2IMG, kk + 8, c0, l16));
-        qa[stp][db] = cat(lds_tr_read(qi, kk, c0, l16), lds_tr_read(qi, kk + 8, c0, l16));
+        oa[stp][db] = cat(tr_read(qi + K2IMG, kk, c0, l16), tr_read(qi + K2IMG, kk + 8, c0, l16));
+        qa[stp][db] = cat(tr_read(qi, kk, c0, l16), tr_read(qi, kk + 8, c0, l16));
       }
     }
 #pragma unroll
@@ -905,8 +854,8 @@ __global__ __launch_bounds__(K3NT, 1) void attn_bwd_dkdv2_kernel(const AttnBwdPa
 
   // LDS-DMA of a tile: wave w fills image rows 4w .. 4w+3 of Q and of dO (one 1-KiB piece each)
   // and its own copy of the tile's 32 lse2 and 32 delta values (3 instructions per wave and tile)
-  const uint32_t smem0 = lds_u32(smem);
-  const int row = 4 * w + g, ch = l16 ^ img_swz(row);
+  const uint32_t smem0 = lds_addr(smem);
+  const int row = 4 * w + g, ch = l16 ^ swz(row);
   const int64_t st_lane = ((l16 & 15) < 8 ? (int64_t)p.B * p.Hq * Sqp : 0) + 4 * (l16 & 7);  // lse2 | delta
   const uint32_t qo = (uint32_t)(row * p.q_ss + ch * 8), oo = (uint32_t)(row * P.do_ss + ch * 8);
   auto dma_tile = [&](int hq, int qt, uint32_t slot_off) __attribute__((always_inline)) {
@@ -962,7 +911,7 @@ __global__ __launch_bounds__(K3NT, 1) void attn_bwd_dkdv2_kernel(const AttnBwdPa
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
         const int c0 = db * 32 + (g & 1) * 16;
-        const bf16x8 a = cat(lds_tr_read(pi, kk, c0, l16), lds_tr_read(pi, kk + 8, c0, l16));
+        const bf16x8 a = cat(tr_read(pi, kk, c0, l16), tr_read(pi, kk + 8, c0, l16));
         acc[db] = mfma32(a, stp ? sb1 : sb0, acc[db]);
       }
     }
@@ -1015,7 +964,7 @@ __global__ __launch_bounds__(K3NT, 1) void attn_bwd_dkdv2_kernel(const AttnBwdPa
 #pragma unroll
         for (int db = 0; db < 4; ++db) {
           const int c0 = db * 32 + (g & 1) * 16;
-          const bf16x8 a = cat(lds_tr_read(qi + K3IMG, kk, c0, l16), lds_tr_read(qi + K3IMG, kk + 8, c0, l16));
+          const bf16x8 a = cat(tr_read(qi + K3IMG, kk, c0, l16), tr_read(qi + K3IMG, kk + 8, c0, l16));
           acc[db] = mfma32(a, stp ? pb1 : pb0, acc[db]);
         }
       }
@@ -1188,9 +1137,9 @@ __global__ __launch_bounds__(Q2NT, 2) void attn_bwd_dq_kernel(const AttnBwdParam
 
   // LDS-DMA of tile t into slot t % Q2NSLOT: wave w fills image rows 8w .. 8w+7 of K and V.
   // Per-lane source offsets are fixed (row 8w + 4k + g, swizzled chunk); only the key base moves.
-  const uint32_t smem0 = lds_u32(smem);
+  const uint32_t smem0 = lds_addr(smem);
   const int row0 = 8 * w + g, row1 = row0 + 4;
-  const int ch0 = l16 ^ img_swz(row0), ch1 = l16 ^ img_swz(row1);
+  const int ch0 = l16 ^ swz(row0), ch1 = l16 ^ swz(row1);
   auto dma_tile = [&](int t, uint32_t slot_off) {
     const int64_t k0r = min(t * Q2N + row0, Sk - 1), k1r = min(t * Q2N + row1, Sk - 1);  // past Sk: masked
     const uint32_t dst = __builtin_amdgcn_readfirstlane(smem0 + slot_off + (uint32_t)(8 * w * 256));
@@ -1265,7 +1214,7 @@ __global__ __launch_bounds__(Q2NT, 2) void attn_bwd_dq_kernel(const AttnBwdParam
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
         const int c0 = db * 32 + (g & 1) * 16;
-        const bf16x8 a = cat(lds_tr_read(ki, kk, c0, l16), lds_tr_read(ki, kk + 8, c0, l16));
+        const bf16x8 a = cat(tr_read(ki, kk, c0, l16), tr_read(ki, kk + 8, c0, l16));
         dq[db] = mfma32(a, sb, dq[db]);
       }
     }

@@ -30,6 +30,7 @@
 #include <stdlib.h>
 
 #include "grt_attn_d64.h"
+#include "grt_attn_dropout.h"
 #include "grt_common.h"
 #include "grt_kernels.h"
 
@@ -37,18 +38,6 @@ namespace grt {
 namespace {
 
 using namespace d64;  // tile geometry, MFMA / LDS helpers (grt_attn_d64.h)
-
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-// identical to attention.hip / attention_f32.hip / ops/_ref.attn_dropout_keep
-__device__ __forceinline__ float drop_factor(const AttnParams& p, uint32_t bh, int q, int k) {
-  uint32_t h = p.drop_seed ^ (bh * 0x9E3779B1u);
-  h = fmix32(h ^ ((uint32_t)q * 0x85EBCA77u));
-  h = fmix32(h ^ ((uint32_t)k * 0xC2B2AE3Du));
-  return h >= p.drop_thresh ? p.drop_scale : 0.f;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Forward: 128 query rows per workgroup (32 per wave), 32-key tiles

@@ -23,8 +23,10 @@
 // contiguous within each 32-lane half.
 #include <stdlib.h>
 
+#include "grt_attn_dropout.h"
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_mfma.h"
 
 namespace grt {
 namespace {
@@ -36,19 +38,6 @@ constexpr float kLn2 = 0.6931471805599453f;
 
 __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-// identical to attention.hip / ops/_ref.attn_dropout_keep
-__device__ __forceinline__ float drop_factor(const AttnParams& p, uint32_t bh, int q, int k) {
-  uint32_t h = p.drop_seed ^ (bh * 0x9E3779B1u);
-  h = fmix32(h ^ ((uint32_t)q * 0x85EBCA77u));
-  h = fmix32(h ^ ((uint32_t)k * 0xC2B2AE3Du));
-  return h >= p.drop_thresh ? p.drop_scale : 0.f;
 }
 
 template <int D>

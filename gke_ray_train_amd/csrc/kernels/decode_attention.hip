@@ -23,16 +23,6 @@
 namespace grt {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void cvt8(const u32x4& v, float (&f)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(v[i] << 16);
-    f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-  }
-}
-
 template <int D, int G>
 __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecodeParams p) {
   constexpr int kLanes = D / 8;           // lanes per key
@@ -63,7 +53,7 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const bf16* qp = (const bf16*)p.q + (int64_t)b * p.q_bs + (int64_t)(hkv * G + g) * p.q_hs + c * 8;
-    cvt8(*reinterpret_cast<const u32x4*>(qp), q[g]);
+    bf16x8_to_f32(*reinterpret_cast<const u32x4*>(qp), q[g]);
 #pragma unroll
     for (int i = 0; i < 8; ++i) q[g][i] *= p.scale_log2;  // scores in log2 units
   }
@@ -77,8 +67,8 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
   }
   for (; j < k1; j += kStep) {
     float kf[8], vf[8];
-    cvt8(kraw, kf);
-    cvt8(vraw, vf);
+    bf16x8_to_f32(kraw, kf);
+    bf16x8_to_f32(vraw, vf);
     if (j + kStep < k1) {
       kraw = *reinterpret_cast<const u32x4*>(Kb + (int64_t)(j + kStep) * p.k_ss);
       vraw = *reinterpret_cast<const u32x4*>(Vb + (int64_t)(j + kStep) * p.v_ss);

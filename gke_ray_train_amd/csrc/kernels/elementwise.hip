@@ -12,6 +12,7 @@
 
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_lds_image.h"
 
 namespace grt {
 namespace {
@@ -128,31 +129,11 @@ __global__ __launch_bounds__(kNT) void swiglu_bwd1_kernel(const T* __restrict__ 
 // The TN weight gradient of the down projection needs h^T (h = silu(gate) * up, [M, F]) and that of
 // the gate/up projection needs dgu^T ([2F, M]). A separate transpose kernel re-reads what these
 // kernels just wrote; here the producing kernel writes both layouts: one workgroup = 64 token rows x
-// 128 columns, the row-major result stored directly and staged in an XOR-swizzled bf16 LDS image
-// (16 chunks of 16 bytes per row) that gfx950's ds_read_b64_tr_b16 reads back transposed, stored as
-// 16-byte row segments of the transposed output (the scheme of transpose.hip).
-typedef __attribute__((address_space(3))) bf16x4 ew_lds_bf16x4_t;
-__device__ __forceinline__ int ew_tswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int ew_toff(int row, int ch) { return row * 256 + 16 * (ch ^ ew_tswz(row)); }
-
-// image [64 rows][128 cols] -> dst rows c0 + (0..127) (row stride ldt), columns r0 .. r0 + 63
-__device__ __forceinline__ void ew_store_transposed(const char* img, bf16* __restrict__ dst, int64_t ldt, int64_t r0) {
-  const int t = threadIdx.x, l16 = t & 15, grp = t >> 4;
-#pragma unroll
-  for (int pp = 0; pp < 2; ++pp) {
-    const int pr = grp + 16 * pp;
-    const int cb = 16 * (pr >> 2), rb = 16 * (pr & 3);
-    bf16x4 q[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int rr = rb + 4 * k + (l16 >> 2), col = cb + 4 * (l16 & 3);
-      q[k] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((ew_lds_bf16x4_t*)(img + ew_toff(rr, col >> 3) + 8 * ((col >> 2) & 1)));
-    }
-    bf16* d = dst + (int64_t)(cb + l16) * ldt + r0 + rb;
-    *reinterpret_cast<bf16x8*>(d) = __builtin_shufflevector(q[0], q[1], 0, 1, 2, 3, 4, 5, 6, 7);
-    *reinterpret_cast<bf16x8*>(d + 8) = __builtin_shufflevector(q[2], q[3], 0, 1, 2, 3, 4, 5, 6, 7);
-  }
-}
+// 128 columns, the row-major result stored directly and staged in the XOR-swizzled bf16 LDS image
+// of grt_lds_image.h, whose store_transposed_64x128 writes it as 16-byte row segments of the
+// transposed output.
+using lds_image::chunk_off;
+using lds_image::store_transposed_64x128;
 
 // out [rows, f] (row stride ldo) and outT [f, rows]; rows % 64 == 0, f % 128 == 0
 __global__ __launch_bounds__(256) void swiglu_fwd_t_kernel(const bf16* __restrict__ gu, bf16* __restrict__ out,
@@ -180,10 +161,10 @@ __global__ __launch_bounds__(256) void swiglu_fwd_t_kernel(const bf16* __restric
       o[j] = static_cast<bf16>(g * sigmoidf_(g) * u);
     }
     *reinterpret_cast<bf16x8*>(out + (r0 + row) * ldo + c0 + ch * 8) = o;
-    *reinterpret_cast<bf16x8*>(img + ew_toff(row, ch)) = o;
+    *reinterpret_cast<bf16x8*>(img + chunk_off(row, ch)) = o;
   }
   __syncthreads();
-  ew_store_transposed(img, outT + (int64_t)c0 * rows, rows, r0);
+  store_transposed_64x128<int64_t>(img, outT + (int64_t)c0 * rows, rows, 0, r0);
 }
 
 // dgu [rows, 2f] and dguT [2f, rows]; rows % 64 == 0, f % 128 == 0
@@ -220,12 +201,12 @@ __global__ __launch_bounds__(256) void swiglu_bwd_t_kernel(const bf16* __restric
     }
     *reinterpret_cast<bf16x8*>(drow + ch * 8) = dg;
     *reinterpret_cast<bf16x8*>(drow + f + ch * 8) = du;
-    *reinterpret_cast<bf16x8*>(img[0] + ew_toff(row, ch)) = dg;
-    *reinterpret_cast<bf16x8*>(img[1] + ew_toff(row, ch)) = du;
+    *reinterpret_cast<bf16x8*>(img[0] + chunk_off(row, ch)) = dg;
+    *reinterpret_cast<bf16x8*>(img[1] + chunk_off(row, ch)) = du;
   }
   __syncthreads();
-  ew_store_transposed(img[0], dguT + (int64_t)c0 * rows, rows, r0);
-  ew_store_transposed(img[1], dguT + (int64_t)(f + c0) * rows, rows, r0);
+  store_transposed_64x128<int64_t>(img[0], dguT + (int64_t)c0 * rows, rows, 0, r0);
+  store_transposed_64x128<int64_t>(img[1], dguT + (int64_t)(f + c0) * rows, rows, 0, r0);
 }
 
 // ------------------------------- GELU (erf) ---------------------------------

@@ -32,43 +32,20 @@
 // rows (ld % 8 == 0).
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_lds_image.h"
 
 #include <type_traits>
 
 namespace grt {
 namespace {
 
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+using namespace lds_image;  // swizzled image, transposed read, LDS-DMA (grt_lds_image.h)
 
 constexpr int TP = 256, TQ = 256, TR = 32, GNT = 512;
 constexpr int kImg = TR * 256;           // one image: 32 rows x 256 bytes = 8 KiB
 constexpr int kSlot = 4 * kImg;          // one half-step: 32 KiB
 constexpr int kSlots = 4;
 constexpr int kGroupRows = 8;
-
-__device__ __forceinline__ int swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int img_off(int row, int ch) { return row * 256 + 16 * (ch ^ swz(row)); }
-
-// 16-lane group reads rows r0..r0+3, columns c0..c0+15; lane i gets column c0 + i.
-__device__ __forceinline__ bf16x4 tr_read(const char* base, int r0, int c0, int l16) {
-  const int q = l16 >> 2, col = c0 + 4 * (l16 & 3);
-  const char* a = base + img_off(r0 + q, col >> 3) + 8 * ((col >> 2) & 1);
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)a);
-}
-__device__ __forceinline__ bf16x8 cat(bf16x4 a, bf16x4 b) {
-  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-// LDS-DMA of 16 bytes per lane to (wave-uniform LDS byte address) + lane * 16. Issued as inline asm
-// so hipcc does not track it: its waitcnt pass would otherwise put vmcnt(0) in front of every LDS
-// read of the loop (it cannot prove the reads miss the in-flight DMA) and serialise the pipeline.
-// The kernel counts vmcnt itself.
-__device__ __forceinline__ void glds16(const void* gptr, uint32_t lds_addr) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-               :: "v"(gptr), "s"(lds_addr) : "memory", "m0");
-}
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)(p);
-}
 
 // MFMA operand: lane (g, l16) gets column c0 + l16, reduction rows rb + 8g .. rb + 8g + 7
 __device__ __forceinline__ bf16x8 frag(const char* img, int rb, int c0, int g, int l16) {
@@ -110,7 +87,7 @@ __global__ __launch_bounds__(GNT, 1) void gemm_tt_kernel(const GemmTTParams p) {
     return Dma{DIAG == 1 ? xsrc : xsrc + h * xstep, DIAG == 1 ? ysrc : ysrc + h * ystep,
                (uint32_t)__builtin_amdgcn_readfirstlane(ldsw + (h % NSLOT) * kSlot)};
   };
-  auto dma = [&](const Dma& a, int k) { glds16(((k & 2) ? a.ys : a.xs) + (k & 1) * 256, a.d + k * kImg); };
+  auto dma = [&](const Dma& a, int k) { lds_dma16(((k & 2) ? a.ys : a.xs) + (k & 1) * 256, a.d + k * kImg); };
 
   f32x4 acc[8][4];
 #pragma unroll

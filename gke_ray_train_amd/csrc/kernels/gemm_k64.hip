@@ -36,6 +36,7 @@
 // multiples of 8 elements, 16-byte aligned bases, every operand byte offset below 2^31.
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_lds_image.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -97,10 +98,6 @@ template <int OFF>
 __device__ __forceinline__ void dma(uint32_t voff, __amdgpu_buffer_rsrc_t rsrc, uint32_t soff, uint32_t mbase) {
   asm volatile("s_add_u32 m0, %2, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
                :: "v"(voff), "s"(rsrc), "s"(mbase), "s"(soff), "i"(OFF) : "memory", "m0", "scc");
-}
-
-__device__ __forceinline__ uint32_t lds_u32(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)(p);
 }
 
 template <typename F, int... I>
@@ -188,7 +185,7 @@ __global__ __launch_bounds__(256, 1) void gemm_k64_kernel(const GemmParams p) {
     soa[q] = (uint32_t)(128 * (q >> 2) + 4 * (q & 3)) * lda2;
     sob[q] = (uint32_t)(128 * (q >> 2) + 4 * (q & 3)) * ldb2;
   }
-  const uint32_t mbase = __builtin_amdgcn_readfirstlane(lds_u32(smem) + w * CH);
+  const uint32_t mbase = __builtin_amdgcn_readfirstlane(lds_image::lds_addr(smem) + w * CH);
   auto rsrc = [](const char* base, int num) __attribute__((always_inline)) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, num, 0x00020000);
   };

@@ -34,6 +34,7 @@
 // multiples of 8 elements, 16-byte aligned bases.
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_lds_image.h"
 
 #include <type_traits>
 
@@ -47,17 +48,8 @@ constexpr int OPB = GT * GS * 2;   // 16 KiB: one operand in one slot
 constexpr int SLOTB = 2 * OPB;     // 32 KiB
 constexpr int kGroupRows = 8;
 
-// LDS-DMA of 16 bytes per lane to (wave-uniform LDS byte address) + lane * 16. Inline asm so hipcc
-// does not count it: its waitcnt pass would otherwise drain vmcnt before every LDS read of the loop.
-// M0 is saved and restored around the DMA (cdna_hip_programming.md §5.7).
-__device__ __forceinline__ void glds16(const void* gptr, uint32_t lds_addr) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gptr), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)(p);
-}
+using namespace lds_image;  // LDS-DMA (the M0-preserving form); TT operands: swizzled image, transposed read
+
 __device__ __forceinline__ void wait_vm(int pending) {
   // pending = DMA instructions of this wave allowed to stay in flight (multiple of 2, <= 8)
   if (pending >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -112,13 +104,13 @@ __global__ __launch_bounds__(GNT, 1) void gemm_nt_kernel(const GemmParams p) {
   const int S = p.K / GS;
   auto dma_a = [&](int j) {
     const uint32_t d = __builtin_amdgcn_readfirstlane(lds0 + (j % RING) * SLOTB);
-    glds16(asrc + j * GS, d);
-    glds16(asrc + astep + j * GS, d + 8192);
+    lds_dma16_keep_m0(asrc + j * GS, d);
+    lds_dma16_keep_m0(asrc + astep + j * GS, d + 8192);
   };
   auto dma_b = [&](int j) {
     const uint32_t d = __builtin_amdgcn_readfirstlane(lds0 + (j % RING) * SLOTB + OPB);
-    glds16(bsrc + j * GS, d);
-    glds16(bsrc + bstep + j * GS, d + 8192);
+    lds_dma16_keep_m0(bsrc + j * GS, d);
+    lds_dma16_keep_m0(bsrc + bstep + j * GS, d + 8192);
   };
 
   f32x4 acc[8][4];
@@ -242,13 +234,7 @@ __device__ __forceinline__ int hswz(int r) { return (r >> 1) & 7; }  // chunk XO
 // TT = true: the weight-gradient form C[P][Q] = sum_r X[r][p] Y[r][q] on token-major operands
 // (a = X [R][P], b = Y [R][Q]): the half-tiles are [64 r][128 p|q] images of 256-B rows (T10 (b)
 // XOR layout, whole cache lines per DMA piece) and the MFMA operands come from
-// ds_read_b64_tr_b16 transposed reads — no transpose pass over dY or X.
-__device__ __forceinline__ int tswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ bf16x4 tt_read(const char* base, int r0, int c0, int l16) {
-  const int q = l16 >> 2, col = c0 + 4 * (l16 & 3);
-  const char* a = base + (r0 + q) * 256 + 16 * ((col >> 3) ^ tswz(r0 + q)) + 8 * ((col >> 2) & 1);
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)a);
-}
+// ds_read_b64_tr_b16 transposed reads (grt_lds_image.h) — no transpose pass over dY or X.
 
 template <int EPI, bool AT, bool BT>
 __global__ __launch_bounds__(GNT, 1) void gemm_h_kernel(const GemmParams p) {
@@ -277,7 +263,7 @@ __global__ __launch_bounds__(GNT, 1) void gemm_h_kernel(const GemmParams p) {
   int64_t a_q, b_q, a_i, b_i, a_t, b_t;  // element offsets per quadrant half / instruction / K-tile
   const int kc_ch = (lane & 7) ^ ((4 * (w & 1) + (lane >> 4)) & 7);
   const int t_row0 = 4 * w + (lane >> 4);
-  const int t_c = (lane & 15) ^ tswz(t_row0);
+  const int t_c = (lane & 15) ^ swz(t_row0);
   if constexpr (!AT) {
     abase = static_cast<const bf16*>(p.a) + (int64_t)(m0 + 8 * w + (lane >> 3)) * p.lda + 8 * kc_ch;
     a_q = 64 * p.lda; a_i = 128 * p.lda; a_t = 64;
@@ -305,12 +291,12 @@ __global__ __launch_bounds__(GNT, 1) void gemm_h_kernel(const GemmParams p) {
     const uint32_t d = __builtin_amdgcn_readfirstlane(lds0 + (t & 1) * BUF + slot * HT);
     if (isA) {
       const bf16* s = abase + q * a_q + t * a_t;
-      glds16(s, d);
-      glds16(s + a_i, d + 8192);
+      lds_dma16_keep_m0(s, d);
+      lds_dma16_keep_m0(s + a_i, d + 8192);
     } else {
       const bf16* s = bbase + q * b_q + t * b_t;
-      glds16(s, d);
-      glds16(s + b_i, d + 8192);
+      lds_dma16_keep_m0(s, d);
+      lds_dma16_keep_m0(s + b_i, d + 8192);
     }
   };
   auto issued = [&](int Q) -> int {  // DMAs issued in phase Q
@@ -342,7 +328,7 @@ __global__ __launch_bounds__(GNT, 1) void gemm_h_kernel(const GemmParams p) {
   };
   auto frag_tm = [&](const char* img, int rb, int ks) -> bf16x8 {
     const int r0 = 32 * ks + 8 * fg;
-    const bf16x4 lo = tt_read(img, r0, rb, fl), hi = tt_read(img, r0 + 4, rb, fl);
+    const bf16x4 lo = tr_read(img, r0, rb, fl), hi = tr_read(img, r0 + 4, rb, fl);
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   };
   auto afragh = [&](const char* img, int rb, int ks) -> bf16x8 {

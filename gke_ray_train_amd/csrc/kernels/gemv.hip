@@ -37,15 +37,6 @@ constexpr int kR = 4;  // weight rows per wave
 // lm_head 165 -> 149 us (7.1 TB/s), the small projections as before (tools/gemv_bench.py,
 // profiles/r5_decode.md)
 constexpr int kKS = 4;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void bf16x8_to_f32(const u32x4& v, float (&f)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(v[i] << 16);
-    f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-  }
-}
 
 __device__ __forceinline__ float silu_f(float g) { return g / (1.f + __expf(-g)); }
 

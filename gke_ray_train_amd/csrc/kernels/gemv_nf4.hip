@@ -31,7 +31,6 @@ namespace grt {
 namespace {
 
 constexpr int kR = 4;  // weight rows per wave
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __constant__ float kLevels[16] = {
     -1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f,

@@ -22,14 +22,14 @@
 // profiles/r2_perf_experiments.md).
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_lds_image.h"
+#include "grt_mfma.h"  // mfma32; the accumulator's row map is acc_row there
 
 namespace grt {
 namespace {
 
-__device__ __forceinline__ f32x16 mfma32x32x16(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-// (accumulator element r of lane half h holds row 8 (r / 4) + 4 h + r % 4 of the 32-row tile)
+using lds_image::lds_addr;
+using lds_image::lds_dma16;
 
 // keep flags of 8 consecutive elements starting at a 4-aligned element index
 __device__ __forceinline__ void keep8(uint64_t key, uint64_t idx0, uint32_t thr, bool (&kp)[8]) {
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const LoraDownParams P) 
           const bf16x8 xf = *reinterpret_cast<const bf16x8*>(xt + (32 * tt + l32) * XS + kk);
 #pragma unroll
           for (int rb = 0; rb < RB; ++rb)
-            acc[rb] = mfma32x32x16(*reinterpret_cast<const bf16x8*>(at + (rb * 32 + l32) * XS + kk), xf, acc[rb]);
+            acc[rb] = mfma32(*reinterpret_cast<const bf16x8*>(at + (rb * 32 + l32) * XS + kk), xf, acc[rb]);
         }
       }
     }
@@ -232,10 +232,6 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const LoraDownParams P) 
 constexpr int LDD_NS = 4;                      // ring slots
 constexpr int LDD_KC = 64;                     // columns per chunk (128-byte rows)
 __device__ __forceinline__ int swz128(int r) { return (r >> 1) & 7; }
-__device__ __forceinline__ void dma16_lds(const void* gptr, uint32_t lds_byte_addr) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-               :: "v"(gptr), "s"(lds_byte_addr) : "memory", "m0");
-}
 
 template <int RB, bool XD>  // R = 32 RB
 __global__ __launch_bounds__(256) void lora_down_dma_kernel(const LoraDownParams P) {
@@ -272,15 +268,15 @@ __global__ __launch_bounds__(256) void lora_down_dma_kernel(const LoraDownParams
     const int r = 8 * RB * w + 8 * q + pr;
     asrc[q] = A + (int64_t)r * P.K + (int64_t)c_lo * LDD_KC + 8 * (pp ^ swz128(r));
   }
-  const uint32_t smem0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)(smem);
+  const uint32_t smem0 = lds_addr(smem);
   auto dma_chunk = [&](int c, int slot) __attribute__((always_inline)) {
     const uint32_t base = smem0 + (uint32_t)(slot * SLOT);
     const uint32_t dx = __builtin_amdgcn_readfirstlane(base + (uint32_t)(16 * w * 128));
     const uint32_t da = __builtin_amdgcn_readfirstlane(base + (uint32_t)(XIMG + 8 * RB * w * 128));
 #pragma unroll
-    for (int q = 0; q < 2; ++q) dma16_lds(xsrc[q] + c * LDD_KC, dx + q * 1024);
+    for (int q = 0; q < 2; ++q) lds_dma16(xsrc[q] + c * LDD_KC, dx + q * 1024);
 #pragma unroll
-    for (int q = 0; q < RB; ++q) dma16_lds(asrc[q] + c * LDD_KC, da + q * 1024);
+    for (int q = 0; q < RB; ++q) lds_dma16(asrc[q] + c * LDD_KC, da + q * 1024);
   };
   // vmcnt: ops younger than chunk t's DMA are nd later chunks' DMAs and ns x_d store groups
   auto wait_chunk = [&](int nd, int ns) __attribute__((always_inline)) {
@@ -332,7 +328,7 @@ __global__ __launch_bounds__(256) void lora_down_dma_kernel(const LoraDownParams
       for (int rb = 0; rb < RB; ++rb) {
         const int ar = rb * 32 + l32;
         const bf16x8 af = *reinterpret_cast<const bf16x8*>(ai + ar * 128 + 16 * (ch ^ swz128(ar)));
-        acc[rb] = mfma32x32x16(af, xf, acc[rb]);
+        acc[rb] = mfma32(af, xf, acc[rb]);
       }
     }
     if (t + LDD_NS - 1 < nch) dma_chunk(t + LDD_NS - 1, (t + LDD_NS - 1) % LDD_NS);
@@ -466,7 +462,7 @@ __global__ __launch_bounds__(256) void lora_dx_kernel(const LoraDxParams P) {
       const int kl = (w >> 1) * 64 + cb * 32;  // column block within the tile
 #pragma unroll
       for (int s = 0; s < SW / 16; ++s)
-        acc[cb] = mfma32x32x16(*reinterpret_cast<const bf16x8*>(aimg + (kl + l32) * RP + 16 * s + 8 * h),
+        acc[cb] = mfma32(*reinterpret_cast<const bf16x8*>(aimg + (kl + l32) * RP + 16 * s + 8 * h),
                                *reinterpret_cast<const bf16x8*>(gimg + tl * RP + 16 * s + 8 * h), acc[cb]);  // D[k][token]
     }
   }

@@ -28,37 +28,13 @@
 
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_lds_image.h"
+#include "grt_mfma.h"
 
 namespace grt {
 namespace {
 
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_t;
-
-__device__ __forceinline__ f32x16 mfma_bf16_32(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-// accumulator element r of lane half hh holds row (r & 3) + 8 (r >> 2) + 4 hh of the 32-row tile
-__device__ __forceinline__ int acc_row32(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
-// [rows][128 x bf16] LDS image, 256 B rows, 16-byte chunks XOR-swizzled so that both the b128 row
-// reads (32 rows, one chunk) and the tr_b16 column reads are conflict-free (attention.hip img_off)
-__device__ __forceinline__ int swz16(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int img_byte(int row, int ch) { return row * 256 + 16 * (ch ^ swz16(row)); }
-__device__ __forceinline__ bf16x4 tr_read(const char* base, int r0, int c0, int l16) {
-  const int q = l16 >> 2, p = l16 & 3;
-  const int col = c0 + 4 * p;
-  const char* a = base + img_byte(r0 + q, col >> 3) + 8 * ((col >> 2) & 1);
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)a);
-}
-__device__ __forceinline__ bf16x8 cat8(bf16x4 a, bf16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
-
-__device__ __forceinline__ void dma16(const void* gptr, uint32_t lds_byte_addr) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-               :: "v"(gptr), "s"(lds_byte_addr) : "memory", "m0");
-}
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)(p);
-}
+using namespace lds_image;  // swizzled image, transposed read, LDS-DMA (grt_lds_image.h)
 
 // ---------------------------------------------------------------------------------------------
 // lora_g
@@ -113,13 +89,13 @@ __global__ __launch_bounds__(256) void lora_g_kernel(const LoraGParams P) {
   for (int q = 0; q < 2; ++q) {
     const int r = 8 * w + 4 * q + g4;
     const int64_t m = min(m0 + r, P.M - 1);
-    asrc[q] = A + m * lda + (int64_t)kt0 * 128 + 8 * (l16 ^ swz16(r));
+    asrc[q] = A + m * lda + (int64_t)kt0 * 128 + 8 * (l16 ^ swz(r));
   }
   const bf16* bsrc[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int r = 16 * w + 4 * q + g4;
-    bsrc[q] = BT + (int64_t)r * ldbt + (int64_t)kt0 * 128 + 8 * (l16 ^ swz16(r));
+    bsrc[q] = BT + (int64_t)r * ldbt + (int64_t)kt0 * 128 + 8 * (l16 ^ swz(r));
   }
   const uint32_t smem0 = lds_addr(smem);
   auto dma_tile = [&](int t, int slot) {
@@ -127,9 +103,9 @@ __global__ __launch_bounds__(256) void lora_g_kernel(const LoraGParams P) {
     const uint32_t da = __builtin_amdgcn_readfirstlane(base + (uint32_t)(8 * w * 256));
     const uint32_t db = __builtin_amdgcn_readfirstlane(base + (uint32_t)(8192 + 16 * w * 256));
 #pragma unroll
-    for (int q = 0; q < 2; ++q) dma16(asrc[q] + t * 128, da + q * 1024);
+    for (int q = 0; q < 2; ++q) lds_dma16(asrc[q] + t * 128, da + q * 1024);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) dma16(bsrc[q] + t * 128, db + q * 1024);
+    for (int q = 0; q < 4; ++q) lds_dma16(bsrc[q] + t * 128, db + q * 1024);
   };
   f32x16 acc0 = f32x16{}, acc1 = f32x16{};
   if (nt > 0) {
@@ -146,11 +122,11 @@ __global__ __launch_bounds__(256) void lora_g_kernel(const LoraGParams P) {
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const int ch = 2 * (2 * w + s2) + hh;
-        const bf16x8 af = *reinterpret_cast<const bf16x8*>(ai + img_byte(l32, ch));
-        const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(bi + img_byte(l32, ch));
-        const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(bi + img_byte(32 + l32, ch));
-        acc0 = mfma_bf16_32(af, b0, acc0);
-        acc1 = mfma_bf16_32(af, b1, acc1);
+        const bf16x8 af = *reinterpret_cast<const bf16x8*>(ai + chunk_off(l32, ch));
+        const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(bi + chunk_off(l32, ch));
+        const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(bi + chunk_off(32 + l32, ch));
+        acc0 = mfma32(af, b0, acc0);
+        acc1 = mfma32(af, b1, acc1);
       }
     }
   }
@@ -159,8 +135,8 @@ __global__ __launch_bounds__(256) void lora_g_kernel(const LoraGParams P) {
   float* part = reinterpret_cast<float*>(smem);  // [4 waves][32 rows][64 cols]
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    part[w * 2048 + acc_row32(r, hh) * 64 + l32] = acc0[r];
-    part[w * 2048 + acc_row32(r, hh) * 64 + 32 + l32] = acc1[r];
+    part[w * 2048 + acc_row(r, hh) * 64 + l32] = acc0[r];
+    part[w * 2048 + acc_row(r, hh) * 64 + 32 + l32] = acc1[r];
   }
   __syncthreads();
   const int row = tid >> 3, c8 = (tid & 7) * 8;
@@ -248,18 +224,18 @@ __global__ __launch_bounds__(256) void lora_tred_kernel(const LoraTredParams P) 
   // past column R (R = 64, or the second image at R = 192) re-read a valid chunk: never consumed.
   const uint32_t smem0 = lds_addr(smem);
   const int row0 = 8 * w + g4, row1 = row0 + 4;
-  const int ch0 = l16 ^ swz16(row0), ch1 = l16 ^ swz16(row1);
+  const int ch0 = l16 ^ swz(row0), ch1 = l16 ^ swz(row1);
   auto dma_tile = [&](int t, int slot) {
     const int64_t r0 = mbeg + 32 * t + row0, r1 = mbeg + 32 * t + row1;
     const uint32_t dst = __builtin_amdgcn_readfirstlane(smem0 + (uint32_t)(slot * SLOT + 8 * w * 256));
-    dma16(A + r0 * lda + 8 * ch0, dst);
-    dma16(A + r1 * lda + 8 * ch1, dst + 1024);
+    lds_dma16(A + r0 * lda + 8 * ch0, dst);
+    lds_dma16(A + r1 * lda + 8 * ch1, dst + 1024);
 #pragma unroll
     for (int hi = 0; hi < NHI; ++hi) {
       const int valid = (R - 128 * hi) >= 128 ? 16 : (R - 128 * hi) / 8;  // chunks of this image inside R
       const int c0 = 128 * hi + 8 * (ch0 % valid), c1 = 128 * hi + 8 * (ch1 % valid);
-      dma16(H + r0 * ldh + c0, dst + (1 + hi) * TR_IMG);
-      dma16(H + r1 * ldh + c1, dst + (1 + hi) * TR_IMG + 1024);
+      lds_dma16(H + r0 * ldh + c0, dst + (1 + hi) * TR_IMG);
+      lds_dma16(H + r1 * ldh + c1, dst + (1 + hi) * TR_IMG + 1024);
     }
   };
 
@@ -280,13 +256,13 @@ __global__ __launch_bounds__(256) void lora_tred_kernel(const LoraTredParams P) 
       for (int stp = 0; stp < 2; ++stp) {
         const int kk = 16 * stp + 4 * hh;
         const int c0 = 32 * w + (g4 & 1) * 16;
-        const bf16x8 a = cat8(tr_read(ai, kk, c0, l16), tr_read(ai, kk + 8, c0, l16));
+        const bf16x8 a = cat(tr_read(ai, kk, c0, l16), tr_read(ai, kk + 8, c0, l16));
 #pragma unroll
         for (int j = 0; j < RT; ++j) {
           const char* hi = ai + TR_IMG * (1 + (j >> 2));
           const int cj = 32 * (j & 3) + (g4 & 1) * 16;
-          const bf16x8 b = cat8(tr_read(hi, kk, cj, l16), tr_read(hi, kk + 8, cj, l16));
-          acc[j] = mfma_bf16_32(a, b, acc[j]);  // D[column of A][column of H]
+          const bf16x8 b = cat(tr_read(hi, kk, cj, l16), tr_read(hi, kk + 8, cj, l16));
+          acc[j] = mfma32(a, b, acc[j]);  // D[column of A][column of H]
         }
       }
     }
@@ -298,7 +274,7 @@ __global__ __launch_bounds__(256) void lora_tred_kernel(const LoraTredParams P) 
 #pragma unroll
   for (int j = 0; j < RT; ++j)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tile[(32 * w + acc_row32(r, hh)) * TS + 32 * j + l32] = acc[j][r];
+    for (int r = 0; r < 16; ++r) tile[(32 * w + acc_row(r, hh)) * TS + 32 * j + l32] = acc[j][r];
   __syncthreads();
   float* ws = P.ws + ((int64_t)ks * P.nbt + pick(P.bo, pt)) * 128 * R;  // this product's plane of the split
   if (!P.transpose) {  // ws[n][j]: thread -> 4 consecutive j of one n

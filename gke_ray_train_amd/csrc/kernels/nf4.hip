@@ -12,6 +12,7 @@
 
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_lds_image.h"
 
 namespace grt {
 namespace {
@@ -160,13 +161,8 @@ __global__ __launch_bounds__(256) void nf4_dequant2_kernel(const uint8_t* __rest
 }
 
 // W^T: one workgroup = a 64 x 128 tile of W. Each thread dequantises 32 weights of one row (16
-// code bytes, one absmax) into a bf16 LDS image (rows of 16 XOR-swizzled 16-byte chunks); the
-// transposed tile leaves through gfx950's ds_read_b64_tr_b16 as 16-byte stores of W^T rows (the
-// scheme of transpose.hip's transpose2_bf16_kernel).
-__device__ __forceinline__ int nf4_tswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int nf4_toff(int row, int ch) { return row * 256 + 16 * (ch ^ nf4_tswz(row)); }
-typedef __attribute__((address_space(3))) bf16x4 nf4_lds_bf16x4_t;
-
+// code bytes, one absmax) into the XOR-swizzled bf16 LDS image of grt_lds_image.h; the transposed
+// tile leaves through its store_transposed_64x128 as 16-byte stores of W^T rows.
 __global__ __launch_bounds__(256) void nf4_dequant_t2_kernel(const uint8_t* __restrict__ q,
                                                              const float* __restrict__ absmax, bf16* __restrict__ wt,
                                                              int rows, int cols) {
@@ -174,7 +170,7 @@ __global__ __launch_bounds__(256) void nf4_dequant_t2_kernel(const uint8_t* __re
   __shared__ __attribute__((aligned(16))) char img[64 * 256];
   nf4_lut_init(lut);
   const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 128;
-  const int t = threadIdx.x, lane = t & 63, l16 = lane & 15;
+  const int t = threadIdx.x;
   {
     const int row = t >> 2, part = t & 3;
     const int64_t e = (int64_t)(r0 + row) * cols + c0 + part * 32;
@@ -188,28 +184,11 @@ __global__ __launch_bounds__(256) void nf4_dequant_t2_kernel(const uint8_t* __re
       bf16x8 v;
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = static_cast<bf16>(o[8 * k + j]);
-      *reinterpret_cast<bf16x8*>(img + nf4_toff(row, part * 4 + k)) = v;
+      *reinterpret_cast<bf16x8*>(img + lds_image::chunk_off(row, part * 4 + k)) = v;
     }
   }
   __syncthreads();
-  const int grp = t >> 4;  // 16 groups; group g handles (column block, row block) pairs g and g + 16
-#pragma unroll
-  for (int pp = 0; pp < 2; ++pp) {
-    const int pr = grp + 16 * pp;
-    const int cb = 16 * (pr >> 2), rb = 16 * (pr & 3);
-    bf16x4 qv[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int rr = rb + 4 * k + (l16 >> 2), col = cb + 4 * (l16 & 3);
-      const char* a = img + nf4_toff(rr, col >> 3) + 8 * ((col >> 2) & 1);
-      qv[k] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((nf4_lds_bf16x4_t*)a);
-    }
-    const bf16x8 o0 = __builtin_shufflevector(qv[0], qv[1], 0, 1, 2, 3, 4, 5, 6, 7);
-    const bf16x8 o1 = __builtin_shufflevector(qv[2], qv[3], 0, 1, 2, 3, 4, 5, 6, 7);
-    bf16* d = wt + (int64_t)(c0 + cb + l16) * rows + r0 + rb;
-    *reinterpret_cast<bf16x8*>(d) = o0;
-    *reinterpret_cast<bf16x8*>(d + 8) = o1;
-  }
+  lds_image::store_transposed_64x128(img, wt, rows, c0, r0);
 }
 
 }  // namespace

@@ -20,6 +20,7 @@
 #include "grt_adam.h"
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_lds_image.h"
 
 namespace grt {
 namespace {
@@ -240,12 +241,8 @@ __global__ __launch_bounds__(kNT) void adamw_kernel(P* __restrict__ p, const G* 
 // One workgroup = a 64 x 128 tile: 4 threads per 256-byte row segment, the updated tile staged in
 // LDS and written back transposed with 32 B row segments. Same update, stochastic rounding and
 // random stream (flat index ioff + row * cols + col) as adamw_kernel.
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_o;
-__device__ __forceinline__ int oswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int ooff(int row, int ch) { return row * 256 + 16 * (ch ^ oswz(row)); }
-
 // tile = 64 rows x 128 columns (cols % 128 == 0); the updated tile goes into the XOR-swizzled LDS
-// image of transpose.hip and is read back transposed with ds_read_b64_tr_b16.
+// image of grt_lds_image.h and leaves through its store_transposed_64x128.
 template <bool FAST>
 __global__ __launch_bounds__(kNT) void adamw_t_kernel(bf16* __restrict__ p, const bf16* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ v,
@@ -307,25 +304,10 @@ __global__ __launch_bounds__(kNT) void adamw_t_kernel(bf16* __restrict__ p, cons
     *reinterpret_cast<f32x4*>(v + o) = vv[0];
     *reinterpret_cast<f32x4*>(v + o + 4) = vv[1];
     *reinterpret_cast<bf16x8*>(p + o) = out;
-    *reinterpret_cast<bf16x8*>(img + ooff(row, ch)) = out;
+    *reinterpret_cast<bf16x8*>(img + lds_image::chunk_off(row, ch)) = out;
   }
   __syncthreads();
-  // W^T: lane i of a 16-lane group gets column cb + i of 4 rows per transposed read
-  const int l16 = tid & 15, grp = tid >> 4;
-#pragma unroll
-  for (int pp = 0; pp < 2; ++pp) {
-    const int pr = grp + 16 * pp;
-    const int cb = 16 * (pr >> 2), rb = 16 * (pr & 3);
-    bf16x4 q[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int rr = rb + 4 * k + (l16 >> 2), col = cb + 4 * (l16 & 3);
-      q[k] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_o*)(img + ooff(rr, col >> 3) + 8 * ((col >> 2) & 1)));
-    }
-    bf16* d = pt + (tc * 128 + cb + l16) * rows + tr * 64 + rb;
-    *reinterpret_cast<bf16x8*>(d) = __builtin_shufflevector(q[0], q[1], 0, 1, 2, 3, 4, 5, 6, 7);
-    *reinterpret_cast<bf16x8*>(d + 8) = __builtin_shufflevector(q[2], q[3], 0, 1, 2, 3, 4, 5, 6, 7);
-  }
+  lds_image::store_transposed_64x128(img, pt, rows, tc * 128, tr * 64);  // W^T
 }
 
 template <typename T>

@@ -83,7 +83,7 @@ def _fmix32(h):
 
 def attn_dropout_keep(seed: int, B: int, H: int, Sq: int, Sk: int, p: float, device=None) -> torch.Tensor:
     """[B, H, Sq, Sk] bool keep-mask of the attention-probability dropout, bit-identical to the
-    counter hash of csrc/kernels/attention.hip (element (b*H + h, q, k))."""
+    counter hash of csrc/include/grt_attn_dropout.h (element (b*H + h, q, k))."""
     thresh = min(_M32, math.ceil(p * 2 ** 32))
     bh = torch.arange(B * H, device=device, dtype=torch.int64).view(B, H, 1, 1)
     q = torch.arange(Sq, device=device, dtype=torch.int64).view(1, 1, Sq, 1)
