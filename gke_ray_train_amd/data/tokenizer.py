@@ -129,7 +129,13 @@ class ByteTokenizer:
         out.append(buf.decode("utf-8", "replace"))
         return "".join(out)
 
-    def __call__(self, text, truncation=False, max_length=None, return_tensors=None, **_):
+    def __call__(self, text, truncation=False, max_length=None, return_tensors=None, padding=False, **_):
+        """One string: its ids and an all-ones mask. A list of strings: one row each; with
+        ``padding=True`` / ``"longest"`` the rows are padded with ``pad_token_id`` to the longest,
+        on ``padding_side``, and the mask marks the real tokens (``return_tensors="pt"`` needs
+        rows of one length, so padding unless they already are)."""
+        if not isinstance(text, str):
+            return self._batch(list(text), truncation, max_length, return_tensors, padding)
         ids = self.encode(text, add_special_tokens=False)
         if truncation and max_length:
             ids = ids[:max_length]
@@ -138,6 +144,31 @@ class ByteTokenizer:
             t = torch.tensor([ids], dtype=torch.long)
             return {"input_ids": t, "attention_mask": torch.ones_like(t)}
         return {"input_ids": ids, "attention_mask": [1] * len(ids)}
+
+    def _batch(self, texts, truncation, max_length, return_tensors, padding):
+        rows = [self.encode(t, add_special_tokens=False) for t in texts]
+        if truncation and max_length:
+            rows = [r[:max_length] for r in rows]
+        mask = [[1] * len(r) for r in rows]
+        if padding not in (False, None, "do_not_pad"):
+            if padding not in (True, "longest"):
+                raise ValueError(f"ByteTokenizer: padding={padding!r} is not supported (True / 'longest')")
+            if self.padding_side not in ("left", "right"):
+                raise ValueError(f"ByteTokenizer: padding_side={self.padding_side!r} (left / right)")
+            if self.pad_token_id is None:
+                raise ValueError("ByteTokenizer: padding needs a pad_token (e.g. tok.pad_token = tok.eos_token)")
+            n = max((len(r) for r in rows), default=0)
+            left = self.padding_side == "left"
+            fill = [([self.pad_token_id] * (n - len(r)), [0] * (n - len(r))) for r in rows]
+            rows = [f + r if left else r + f for r, (f, _) in zip(rows, fill)]
+            mask = [z + m if left else m + z for m, (_, z) in zip(mask, fill)]
+        if return_tensors == "pt":
+            import torch
+            if len({len(r) for r in rows}) > 1:
+                raise ValueError("ByteTokenizer: rows of unequal length need padding=True for return_tensors='pt'")
+            return {"input_ids": torch.tensor(rows, dtype=torch.long).view(len(rows), -1),
+                    "attention_mask": torch.tensor(mask, dtype=torch.long).view(len(rows), -1)}
+        return {"input_ids": rows, "attention_mask": mask}
 
     def apply_chat_template(self, messages, tokenize=False, add_generation_prompt=False):
         s = self.bos_token

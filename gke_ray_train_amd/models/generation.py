@@ -16,6 +16,12 @@ current position (RoPE position array and the KV-cache write index) and the per-
 length, which the flash kernel takes as its padding mask (``seqlens_k``) over the full-length
 cache, so the kernel's tile loop still covers only the keys written so far.
 
+Both are per batch row, which is what a padded batch (``attention_mask``) uses: the prompts are
+compacted to column 0 and prefilled as one causal [B, longest] block, each row's logits are taken
+at its own last token, and row b then decodes at position len_b + t into cache slot len_b + t
+(over the K / V the prefill left there for the filler behind a short row) with len_b + t + 1 valid
+keys. No kernel knows about padding.
+
 With a sampler the step ends in ``sample_logits`` (csrc/kernels/sample.hip): greedy argmax or a
 temperature / top-k / top-p draw with counter-based noise, plus the loop's bookkeeping (pad after
 EOS, finished flags, the next step's input id, the output column), so ``generate()`` is
@@ -44,9 +50,54 @@ class KVCache:
         self.v = [torch.zeros(B, max_len, hkv, hd, device=device, dtype=dtype) for _ in range(cfg.num_hidden_layers)]
         self.len = 0
         self.max_len = max_len
+        # per-row token counts [B] int32 after a masked (ragged) prefill; ``len`` is then the longest
+        # row's, which is what the fullness checks compare with ``max_len``
+        self.lens: Optional[torch.Tensor] = None
 
 
-def _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache: KVCache, li: int):
+@dataclass
+class _MaskRows:
+    """A non-trivial attention mask, read on the host: row b's tokens are the columns
+    ``start[b] ... start[b] + lens[b] - 1`` of the padded batch."""
+    start: List[int]
+    lens: List[int]
+
+
+def _mask_rows(attention_mask, B: int, S: int) -> Optional[_MaskRows]:
+    """Validate an HF-style ``attention_mask`` [B, S] (bool / integer, any device; one host read):
+    each row's ones must be one contiguous run of at least one token, with the padding on the left,
+    on the right or on both sides. ``None`` for no mask or an all-ones mask (nothing to do)."""
+    if attention_mask is None or isinstance(attention_mask, _MaskRows):
+        return attention_mask
+    m = torch.as_tensor(attention_mask)
+    if tuple(m.shape) != (B, S):
+        raise ValueError(f"attention_mask has shape {tuple(m.shape)}, input_ids has {(B, S)}")
+    m = (m != 0).cpu()
+    if bool(m.all()):
+        return None
+    lens = m.sum(1).tolist()
+    start = m.int().argmax(1).tolist()
+    for b, (a, n) in enumerate(zip(start, lens)):
+        if n == 0:
+            raise ValueError(f"attention_mask row {b} is all zeros: every row needs at least one token")
+        if not bool(m[b, a:a + n].all()):
+            raise ValueError(f"attention_mask row {b} has a hole: its ones must form one contiguous run")
+    return _MaskRows(start, lens)
+
+
+def _compact(ids: torch.Tensor, rows: _MaskRows) -> torch.Tensor:
+    """Row b's masked tokens moved to columns 0 ... lens[b] - 1 of a [B, max lens] block; the
+    filler behind a short row is id 0, whatever the pad columns held."""
+    j = torch.arange(max(rows.lens), device=ids.device)[None, :]
+    start = torch.tensor(rows.start, device=ids.device)[:, None]
+    lens = torch.tensor(rows.lens, device=ids.device)[:, None]
+    picked = ids.gather(1, (start + j).clamp_(max=ids.shape[1] - 1))
+    return torch.where(j < lens, picked, torch.zeros_like(picked))
+
+
+def _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache: KVCache, li: int, row_pos=None):
+    """``row_pos`` [B] int32: the one-token step of a ragged cache, row b's token at position and
+    cache slot row_pos[b]; without it the S tokens of every row sit at pos0 ... pos0 + S - 1."""
     attn = layer.self_attn
     eps = layer.input_layernorm.eps
     if residual is None:
@@ -56,7 +107,7 @@ def _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache: KVCache, li: in
         x, residual = ops.add_rms_norm(h, residual, layer.input_layernorm.weight, eps)
     qkv = attn.qkv_proj(x)
     hq, hkv, D = attn.hq, attn.hkv, attn.hd
-    pos = torch.arange(pos0, pos0 + S, device=h.device, dtype=torch.int32).repeat(B)
+    pos = row_pos if row_pos is not None else torch.arange(pos0, pos0 + S, device=h.device, dtype=torch.int32).repeat(B)
     if _fused_ok(qkv, cache, li):
         # RoPE of q / k and the cache append of k / v in one kernel (rope_append, elementwise.hip)
         q = _native.kernels().rope_append(qkv.contiguous(), cos, sin, pos, hq, hkv, D, cos.shape[0],
@@ -66,11 +117,19 @@ def _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache: KVCache, li: in
         q = _ref.apply_rope(x3[:, :hq], cos, sin, pos)
         k = _ref.apply_rope(x3[:, hq:hq + hkv], cos, sin, pos)
         v = qkv.view(B, S, hq + 2 * hkv, D)[:, :, hq + hkv:]
-        cache.k[li][:, pos0:pos0 + S] = k.view(B, S, hkv, D)
-        cache.v[li][:, pos0:pos0 + S] = v
+        if row_pos is None:
+            cache.k[li][:, pos0:pos0 + S] = k.view(B, S, hkv, D)
+            cache.v[li][:, pos0:pos0 + S] = v
+        else:
+            b = torch.arange(B, device=h.device)
+            cache.k[li][b, row_pos.long()] = k.view(B, hkv, D)
+            cache.v[li][b, row_pos.long()] = v[:, 0]
     kk = cache.k[li][:, :pos0 + S]
     vv = cache.v[li][:, :pos0 + S]
-    o = ops.flash_attention(q.view(B, S, hq, D), kk, vv, causal=True)
+    if row_pos is None:
+        o = ops.flash_attention(q.view(B, S, hq, D), kk, vv, causal=True)
+    else:  # slots past a short row's own tokens hold the prefill's filler: masked by the valid length
+        o = ops.flash_attention(q.view(B, 1, hq, D), kk, vv, causal=False, seqlens_k=row_pos + 1)
     h = attn.o_proj(o.reshape(B * S, hq * D))
     x, residual = ops.add_rms_norm(h, residual, layer.post_attention_layernorm.weight, eps)
     return _mlp(layer.mlp, x), residual
@@ -98,9 +157,28 @@ def _mlp(mlp, x):
 
 
 @torch.no_grad()
-def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
-    """Run `ids` [B, S] at positions cache.len ... ; returns last-position logits [B, V]."""
+def forward_cached(model, ids: torch.Tensor, cache: KVCache, attention_mask=None) -> torch.Tensor:
+    """Run `ids` [B, S] at positions cache.len ... ; returns last-position logits [B, V].
+
+    With a non-trivial ``attention_mask`` [B, S] (prefill of an empty cache only) row b's prompt is
+    its masked tokens at positions 0 ... len_b - 1: the rows are compacted to column 0 and run as one
+    causal block, whose filler behind a short row comes after that row's tokens and so stays hidden
+    from them; the logits are those of each row's last real token. The cache is ragged from then on
+    (``cache.lens``): each later call takes one token per row, at position and cache slot len_b
+    (over the filler's K / V), attending to that row's len_b + 1 keys."""
     B, S = ids.shape
+    rows = _mask_rows(attention_mask, B, S)
+    row_pos = None
+    if rows is not None:
+        if cache.len != 0:
+            raise ValueError(f"forward_cached: an attention_mask with padding needs an empty cache (prefill), "
+                             f"this one holds {cache.len} tokens")
+        ids = _compact(ids, rows)
+        S = ids.shape[1]
+    elif cache.lens is not None:
+        if S != 1:
+            raise ValueError(f"forward_cached: a ragged cache takes one token per row and call, got {S}")
+        row_pos = cache.lens
     pos0 = cache.len
     if pos0 + S > cache.max_len:  # rope_append writes no cache row past max_len: refuse, don't truncate
         raise ValueError(f"KV cache overflow: {pos0} cached + {S} new tokens > max_len {cache.max_len}")
@@ -108,9 +186,15 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
     h = model.model.embed_tokens(ids).view(B * S, -1)
     residual = None
     for li, layer in enumerate(model.model.layers):
-        h, residual = _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache, li)
+        h, residual = _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache, li, row_pos)
     x, _ = ops.add_rms_norm(h, residual, model.model.norm.weight, model.model.norm.eps)
-    last = x.view(B, S, -1)[:, -1]
+    if rows is not None:
+        cache.lens = torch.tensor(rows.lens, dtype=torch.int32, device=ids.device)
+        last = x.view(B, S, -1)[torch.arange(B, device=ids.device), cache.lens.long() - 1]
+    else:
+        last = x.view(B, S, -1)[:, -1]
+        if row_pos is not None:
+            cache.lens = row_pos + 1
     cache.len += S
     return model.lm_head(last).float()
 
@@ -126,7 +210,7 @@ def _graph_layer_step(layer, h, residual, B, cos, sin, cache: KVCache, li: int, 
         x, residual = ops.add_rms_norm(h, residual, layer.input_layernorm.weight, eps)
     qkv = attn.qkv_proj(x)
     hq, hkv, D = attn.hq, attn.hkv, attn.hd
-    # the new token's position is its cache slot (pos_b == pos_l for every row)
+    # the new token's position is its cache slot, one per row (rows differ after a masked prefill)
     q = _native.kernels().rope_append(qkv.contiguous(), cos, sin, pos_b, hq, hkv, D, cos.shape[0],
                                       cache.k[li], cache.v[li], 1)
     o = ops.flash_attention(q.view(B, 1, hq, D), cache.k[li], cache.v[li], causal=False, seqlens_k=lens)
@@ -283,12 +367,20 @@ class GraphDecoder:
         self._sample(logits)
 
     @torch.no_grad()
-    def prefill(self, input_ids: torch.Tensor) -> torch.Tensor:
-        logits = forward_cached(self.model, input_ids, self.cache)
+    def prefill(self, input_ids: torch.Tensor, attention_mask=None) -> torch.Tensor:
+        """Eager prefill. With a padded batch (``attention_mask``, see ``forward_cached``) every
+        row then decodes from its own length: the step's position and valid-length tensors differ
+        per row, the captured step itself is the same."""
+        logits = forward_cached(self.model, input_ids, self.cache, attention_mask)
         n = self.cache.len
-        self.pos_b.fill_(n)
         self.pos_l.fill_(n)
-        self.lens.fill_(n + 1)
+        if self.cache.lens is None:
+            self.pos_b.fill_(n)
+            self.lens.fill_(n + 1)
+        else:
+            self.pos_b.copy_(self.cache.lens)
+            self.lens.copy_(self.cache.lens + 1)
+            self.cache.lens = self.pos_b  # the replays advance it
         return logits
 
     @torch.no_grad()
@@ -391,6 +483,15 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              seed: Optional[int] = None, device_loop: Optional[bool] = None, **_):
     """Returns [B, prompt + generated] token ids (HF ``generate`` output convention).
 
+    ``attention_mask`` [B, S] (bool / integer, HF semantics) batches prompts of unequal length: row
+    b's prompt is its masked tokens (one contiguous run; padding left, right or on both sides) at
+    positions 0 ... len_b - 1, its t-th new token sits at position len_b + t and attends to that
+    row's prompt and earlier new tokens only, and the ids in the pad columns influence nothing. A
+    greedy row gives the tokens it gives alone. The result is ``input_ids`` as given (pads
+    included) followed by the generated columns. ``None`` or all ones: no padding. A hole, an
+    all-zero row or another shape raises ``ValueError``. Every decode path takes it (graph with
+    either loop, eager): the per-row position and valid-length tensors of the step differ per row.
+
     A bf16 model on the GPU with head_dim 128 or 64 (``llama3.2-1b``) decodes through the HIP-graph
     decoder by default (fused RoPE epilogue of the qkv GEMV, split-K decode attention at either
     width). ``use_graph=False`` gives the eager step; ``GRT_DECODE_ATTN=0`` sends the one-token
@@ -411,6 +512,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     was = model.training
     model.eval()
     B, S = input_ids.shape
+    rows = _mask_rows(attention_mask, B, S)
+    P = S if rows is None else max(rows.lens)  # the longest prompt: the cache holds P + max_new_tokens
     eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
     eos_t = torch.tensor(sorted(eos), device=input_ids.device) if eos else None
     graph = use_graph if use_graph is not None else _graph_ok(model, input_ids)
@@ -429,8 +532,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     if can and (device_loop if device_loop is not None else _DEVICE_SAMPLER):
         cfg = SamplerConfig(max_new_tokens=max_new_tokens, do_sample=do_sample, temperature=temperature, top_k=top_k,
                             top_p=top_p, seed=seed, eos_ids=tuple(sorted(eos)), pad_id=pad_token_id)
-        dec = GraphDecoder(model, B, S + max_new_tokens, sampler=cfg)
-        dec.first_token(dec.prefill(input_ids))
+        dec = GraphDecoder(model, B, P + max_new_tokens, sampler=cfg)
+        dec.first_token(dec.prefill(input_ids, rows))
         done = 1
         while done < max_new_tokens:
             # replays up to the next multiple of sync_every tokens, then one host read
@@ -447,14 +550,14 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
             model.train()
         return torch.cat([input_ids, dec.out[:, :done]], 1)
     if graph:
-        dec = GraphDecoder(model, B, S + max_new_tokens)
-        logits = dec.prefill(input_ids)
+        dec = GraphDecoder(model, B, P + max_new_tokens)
+        logits = dec.prefill(input_ids, rows)
         forward = dec.step
     else:
         p = next(model.parameters())
-        cache = KVCache(model.config, B, S + max_new_tokens, input_ids.device,
+        cache = KVCache(model.config, B, P + max_new_tokens, input_ids.device,
                         p.dtype if p.dtype in (torch.bfloat16, torch.float32) else torch.bfloat16)
-        logits = forward_cached(model, input_ids, cache)
+        logits = forward_cached(model, input_ids, cache, rows)
 
         def forward(nxt):
             return forward_cached(model, nxt[:, None], cache)

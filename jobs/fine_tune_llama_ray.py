@@ -38,8 +38,13 @@ def _load_base(model_id, device, dtype, seed=0):
 
 
 def run_inference_comparison(original_model_id, path_to_fine_tuned_model, eval_rows, max_seq_len, results_output_dir,
-                             device, max_new_generation_tokens=150, tokenizer=None):
-    """Greedy generation of the original vs fine-tuned model on 'window functions' samples."""
+                             device, max_new_generation_tokens=150, tokenizer=None, batch_size=1):
+    """Greedy generation of the original vs fine-tuned model on 'window functions' samples.
+
+    ``batch_size`` = k sends the prompts of k samples through one ``generate`` call per model,
+    left-padded with an attention mask; 1 (the default) is one call per sample, as the reference."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
     from gke_ray_train_amd.data.tokenizer import ByteTokenizer
     from gke_ray_train_amd.trainer.sft_data import format_chat_sample
     from gke_ray_train_amd.models.hub import from_pretrained
@@ -54,18 +59,28 @@ def run_inference_comparison(original_model_id, path_to_fine_tuned_model, eval_r
     results = []
     eos = [tok.eos_token_id, tok.convert_tokens_to_ids("<|eot_id|>")]
     budget = max(50, max_seq_len - max_new_generation_tokens) if max_seq_len > max_new_generation_tokens else max(50, max_seq_len // 2)
-    for i, s in enumerate(samples):
-        prompt = format_chat_sample(s, tok, with_answer=False)["text"]
-        ids = torch.tensor([tok.encode(prompt)[:budget]], device=device)
+    pad = tok.eos_token_id  # pad = eos, as the reference tokenizer is set up
+    for i0 in range(0, len(samples), batch_size):
+        chunk = samples[i0:i0 + batch_size]
+        prompts = [format_chat_sample(s, tok, with_answer=False)["text"] for s in chunk]
+        rows = [tok.encode(p)[:budget] for p in prompts]
+        kw = {}
+        if len(rows) == 1:
+            ids = torch.tensor(rows, device=device)
+        else:  # one left-padded batch: generate() decodes every row from its own length
+            n = max(len(r) for r in rows)
+            ids = torch.tensor([[pad] * (n - len(r)) + r for r in rows], device=device)
+            kw["attention_mask"] = torch.tensor([[0] * (n - len(r)) + [1] * len(r) for r in rows], device=device)
         outs = {}
         for name, m in (("original", orig), ("fine_tuned", tuned)):
-            g = m.generate(ids, max_new_tokens=max_new_generation_tokens, eos_token_id=eos, pad_token_id=tok.eos_token_id)
-            outs[name] = tok.decode(g[0, ids.shape[1]:].tolist(), skip_special_tokens=True).strip()
-        results.append({"id": s.get("id", f"unknown_id_{i}"), "schema_context": s.get("sql_context", ""),
-                        "question_prompt": s.get("sql_prompt", ""), "original_model_input_prompt": prompt,
-                        "fine_tuned_model_input_prompt": prompt, "ground_truth_sql": s.get("sql", ""),
-                        "original_model_sql_response": outs["original"],
-                        "fine_tuned_model_sql_response": outs["fine_tuned"]})
+            g = m.generate(ids, max_new_tokens=max_new_generation_tokens, eos_token_id=eos, pad_token_id=pad, **kw)
+            outs[name] = [tok.decode(r[ids.shape[1]:].tolist(), skip_special_tokens=True).strip() for r in g]
+        for j, (s, prompt) in enumerate(zip(chunk, prompts)):
+            results.append({"id": s.get("id", f"unknown_id_{i0 + j}"), "schema_context": s.get("sql_context", ""),
+                            "question_prompt": s.get("sql_prompt", ""), "original_model_input_prompt": prompt,
+                            "fine_tuned_model_input_prompt": prompt, "ground_truth_sql": s.get("sql", ""),
+                            "original_model_sql_response": outs["original"][j],
+                            "fine_tuned_model_sql_response": outs["fine_tuned"][j]})
     os.makedirs(results_output_dir, exist_ok=True)
     path = os.path.join(results_output_dir, "inference_comparison_results.json")
     with open(path, "w") as f:
