@@ -1070,20 +1070,26 @@ void rope_attn_bwd_d64(const Tensor& dout, const Tensor& qkv, const Tensor& cos,
 // Split-K decode attention (decode_attention.hip). D is the binding's head dim: attn_decode is the
 // head_dim-128 entry point and refuses anything else, attn_decode_d64 the head_dim-64 one.
 Tensor attn_decode_impl(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& seqlens_k,
-                        double scale, int64_t D, const char* op, std::vector<Tensor>* partials = nullptr) {
+                        double scale, int64_t D, const char* op, std::vector<Tensor>* partials = nullptr,
+                        bool multi = false) {
   check_bshd(q, "q");
   check_bshd(k, "k");
   check_bshd(v, "v");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16,
               op, ": bf16");
   TORCH_CHECK(q.size(3) == D && k.size(3) == D && v.size(3) == D, op, ": head_dim ", D);
-  TORCH_CHECK(q.size(1) == 1, op, ": one query token per sequence");
+  if (multi) {
+    TORCH_CHECK(q.size(1) >= 2 && q.size(1) <= 4, op, ": 2 to 4 query tokens per sequence, got ", q.size(1));
+  } else {
+    TORCH_CHECK(q.size(1) == 1, op, ": one query token per sequence");
+  }
+  const int64_t T = q.size(1);
   TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0), op, ": k/v shapes");
   const int64_t Hq = q.size(2), Hkv = k.size(2);
   TORCH_CHECK(Hq % Hkv == 0, op, ": Hq % Hkv");
   const int64_t G = Hq / Hkv;
   TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, op, ": GQA group must be 1, 2, 4 or 8");
-  if (D == 64) {
+  if (D == 64 || multi) {
     // the kernel reads q / k / v with 16-byte loads at any (batch, key, head) offset
     for (const Tensor* t : {&q, &k, &v}) {
       TORCH_CHECK(t->device() == q.device(), op, ": q / k / v on one device");
@@ -1091,7 +1097,7 @@ Tensor attn_decode_impl(const Tensor& q, const Tensor& k, const Tensor& v, const
                   op, ": every stride a multiple of 8 elements, unit head_dim stride");
       TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, op, ": 16-byte aligned base pointers");
     }
-    TORCH_CHECK(k.size(1) <= INT32_MAX && q.size(0) * Hq <= INT32_MAX, op, ": dims");
+    TORCH_CHECK(k.size(1) <= INT32_MAX && q.size(0) * T * Hq <= INT32_MAX, op, ": dims");
   }
   c10::OptionalDeviceGuard g(q.device());
   grt::AttnDecodeParams p{};
@@ -1102,24 +1108,29 @@ Tensor attn_decode_impl(const Tensor& q, const Tensor& k, const Tensor& v, const
   p.k_bs = k.stride(0); p.k_ss = k.stride(1); p.k_hs = k.stride(2);
   p.v_bs = v.stride(0); p.v_ss = v.stride(1); p.v_hs = v.stride(2);
   p.o_bs = o.stride(0); p.o_hs = o.stride(2);
+  p.T = (int)T; p.q_ts = q.stride(1); p.o_ts = o.stride(1);
   p.B = (int)q.size(0); p.Hq = (int)Hq; p.Hkv = (int)Hkv; p.Sk = (int)k.size(1);
   p.NS = grt::attn_decode_splits(p.B, p.Hkv, p.Sk, (int)D);
   p.seqlens_k = nullptr;
   if (seqlens_k.has_value()) {
     check_contig(*seqlens_k, "seqlens_k");
     TORCH_CHECK(seqlens_k->scalar_type() == at::kInt && seqlens_k->numel() == q.size(0), "seqlens_k int32 [B]");
-    if (D == 64) TORCH_CHECK(seqlens_k->device() == q.device(), op, ": seqlens_k on q's device");
+    if (D == 64 || multi) TORCH_CHECK(seqlens_k->device() == q.device(), op, ": seqlens_k on q's device");
     p.seqlens_k = seqlens_k->data_ptr<int32_t>();
   }
   p.scale_log2 = (float)(scale * 1.4426950408889634);
-  auto ws = at::empty({(int64_t)p.B * Hq * p.NS * (D + 2)}, q.options().dtype(at::kFloat));
+  const int64_t rows = (int64_t)p.B * T * Hq;  // [B, T, Hq] partial states per split
+  auto ws = at::empty({rows * p.NS * (D + 2)}, q.options().dtype(at::kFloat));
   p.part_o = ws.data_ptr<float>();
-  p.part_m = p.part_o + (int64_t)p.B * Hq * p.NS * D;
-  p.part_l = p.part_m + (int64_t)p.B * Hq * p.NS;
-  if (D == 64) grt::attn_decode_d64(p, cur_stream(q));
+  p.part_m = p.part_o + rows * p.NS * D;
+  p.part_l = p.part_m + rows * p.NS;
+  if (multi) {
+    if (D == 64) grt::attn_decode_multi_d64(p, cur_stream(q));
+    else grt::attn_decode_multi(p, cur_stream(q));
+  } else if (D == 64) grt::attn_decode_d64(p, cur_stream(q));
   else grt::attn_decode(p, cur_stream(q));
   if (partials) {
-    const int64_t n = (int64_t)p.B * Hq * p.NS;
+    const int64_t n = rows * p.NS;
     *partials = {ws.narrow(0, 0, n * D).view({p.B, Hq, p.NS, D}), ws.narrow(0, n * D, n).view({p.B, Hq, p.NS}),
                  ws.narrow(0, n * D + n, n).view({p.B, Hq, p.NS})};
   }
@@ -1133,6 +1144,18 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const opti
 Tensor attn_decode_d64(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& seqlens_k,
                        double scale) {
   return attn_decode_impl(q, k, v, seqlens_k, scale, 64, "attn_decode_d64");
+}
+
+// Verify step of speculative decoding: q [B, T, Hq, D], T in 2..4, whose keys are the last T of each
+// row; token t attends keys [0, seqlens_k[b] - (T - 1 - t)) (seqlens_k absent: all Sk keys are valid).
+Tensor attn_decode_multi(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& seqlens_k,
+                         double scale) {
+  return attn_decode_impl(q, k, v, seqlens_k, scale, 128, "attn_decode_multi", nullptr, true);
+}
+
+Tensor attn_decode_multi_d64(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& seqlens_k,
+                             double scale) {
+  return attn_decode_impl(q, k, v, seqlens_k, scale, 64, "attn_decode_multi_d64", nullptr, true);
 }
 
 // test support: attn_decode_d64 plus its per-split partial states, [o, part_o [B, Hq, NS, 64],
@@ -1374,7 +1397,8 @@ Tensor sample_logits(const Tensor& logits, bool do_sample, double temperature, i
                      const optional<Tensor>& counter, const optional<Tensor>& keep_mask,
                      const optional<Tensor>& finished, const optional<Tensor>& finish_step,
                      const optional<Tensor>& step, const optional<Tensor>& next_ids, const optional<Tensor>& out,
-                     const optional<Tensor>& eos_ids, const optional<int64_t>& pad_id, int64_t max_steps) {
+                     const optional<Tensor>& eos_ids, const optional<int64_t>& pad_id, int64_t max_steps,
+                     bool candidates) {
   check_cuda(logits, "logits");
   const grt::DType dt = dtype_of(logits);
   TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1, "sample_logits: logits [B, V], B, V >= 1");
@@ -1413,6 +1437,8 @@ Tensor sample_logits(const Tensor& logits, bool do_sample, double temperature, i
   TORCH_CHECK(state == given(finish_step) && state == given(step) && state == given(out),
               "sample_logits: finished, finish_step, step and out come together");
   TORCH_CHECK(state || (!given(eos_ids) && !pad_id.has_value()), "sample_logits: eos_ids / pad_id need the state tensors");
+  TORCH_CHECK(!candidates || !state, "sample_logits: candidates mode takes no state tensors");
+  a.candidates = candidates;
   c10::OptionalDeviceGuard dg(logits.device());
   Tensor tokens;
   if (given(next_ids)) {
@@ -1447,6 +1473,53 @@ Tensor sample_logits(const Tensor& logits, bool do_sample, double temperature, i
   }
   grt::sample_logits(logits.data_ptr(), dt, a, cur_stream(logits));
   return tokens;
+}
+
+// Accept + draft step of speculative decoding (spec.hip), one sequence, K = drafts.numel() in 1..3.
+// Every tensor lives on cand's device and is updated in place; `drafts` holds the drafts the verify
+// step was fed and receives the next step's. plan: test hook (the drafts for token n are plan[n ..]).
+void spec_advance(const Tensor& cand, const Tensor& drafts, const Tensor& ids, const Tensor& pos, const Tensor& lens,
+                  const Tensor& n_step, const Tensor& counter, const Tensor& finished, const Tensor& finish_step,
+                  const Tensor& done, const Tensor& out, const Tensor& hist, int64_t prompt_len, int64_t max_new,
+                  int64_t max_ngram, int64_t vocab, const optional<Tensor>& plan, const optional<Tensor>& eos_ids) {
+  check_cuda(cand, "cand");
+  const int64_t K = drafts.numel();
+  TORCH_CHECK(K >= 1 && K <= grt::kSpecMaxDrafts, "spec_advance: 1 to ", grt::kSpecMaxDrafts, " drafts, got ", K);
+  TORCH_CHECK(max_ngram >= 1 && max_ngram <= INT32_MAX && prompt_len >= 0 && max_new >= 1 && vocab >= 1,
+              "spec_advance: max_ngram, max_new, vocab >= 1 and prompt_len >= 0");
+  auto vec = [&](const Tensor& t, const char* name, at::ScalarType st, int64_t n, bool exact) {
+    check_contig(t, name);
+    TORCH_CHECK(t.scalar_type() == st && (exact ? t.numel() == n : t.numel() >= n) && t.device() == cand.device(),
+                "spec_advance: ", name, " must hold ", n, " element(s) of its type on cand's device");
+    return t.data_ptr();
+  };
+  grt::SpecAdvanceArgs a{};
+  a.cand = (const int64_t*)vec(cand, "cand", at::kLong, K + 1, true);
+  a.drafts = (int64_t*)vec(drafts, "drafts", at::kLong, K, true);
+  a.ids = (int64_t*)vec(ids, "ids", at::kLong, K + 1, true);
+  a.pos = (int32_t*)vec(pos, "pos", at::kInt, K + 1, true);
+  a.lens = (int32_t*)vec(lens, "lens", at::kInt, 1, true);
+  a.n_step = (int64_t*)vec(n_step, "n_step", at::kLong, 1, true);
+  a.counter = (int64_t*)vec(counter, "counter", at::kLong, 1, true);
+  TORCH_CHECK(finished.scalar_type() == at::kBool || finished.scalar_type() == at::kByte, "spec_advance: finished bool / uint8");
+  a.finished = (uint8_t*)vec(finished, "finished", finished.scalar_type(), 1, true);
+  a.finish_step = (int64_t*)vec(finish_step, "finish_step", at::kLong, 1, true);
+  TORCH_CHECK(done.scalar_type() == at::kBool || done.scalar_type() == at::kByte, "spec_advance: done bool / uint8");
+  a.done = (uint8_t*)vec(done, "done", done.scalar_type(), 1, true);
+  a.out = (int64_t*)vec(out, "out", at::kLong, max_new, false);
+  a.hist = (int64_t*)vec(hist, "hist", at::kLong, prompt_len + max_new, false);
+  a.prompt_len = prompt_len, a.max_new = max_new, a.K = (int)K, a.N = (int)max_ngram, a.vocab = vocab;
+  if (plan.has_value() && plan->defined()) {
+    a.plan = (const int64_t*)vec(*plan, "plan", at::kLong, 0, false);
+    a.plan_len = plan->numel();
+  }
+  if (eos_ids.has_value() && eos_ids->defined()) {
+    TORCH_CHECK(eos_ids->numel() <= grt::kSampleMaxEos, "spec_advance: at most ", grt::kSampleMaxEos, " EOS ids");
+    a.eos = (const int64_t*)vec(*eos_ids, "eos_ids", at::kLong, eos_ids->numel(), true);
+    a.n_eos = (int)eos_ids->numel();
+  }
+  c10::OptionalDeviceGuard dg(cand.device());
+  grt::spec_advance(a, cur_stream(cand));
 }
 
 // y [M, N] = x W^T straight from the NF4 codes of W [N, K] (gemv_nf4.hip; blocksize 64, fp32 absmax),
@@ -1838,7 +1911,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("top_k") = 0, py::arg("top_p") = 1.0, py::arg("seed") = 0, py::arg("counter") = py::none(),
         py::arg("keep_mask") = py::none(), py::arg("finished") = py::none(), py::arg("finish_step") = py::none(),
         py::arg("step") = py::none(), py::arg("next_ids") = py::none(), py::arg("out") = py::none(),
-        py::arg("eos_ids") = py::none(), py::arg("pad_id") = py::none(), py::arg("max_steps") = 1);
+        py::arg("eos_ids") = py::none(), py::arg("pad_id") = py::none(), py::arg("max_steps") = 1,
+        py::arg("candidates") = false);
+  m.def("spec_advance", &spec_advance, py::arg("cand"), py::arg("drafts"), py::arg("ids"), py::arg("pos"),
+        py::arg("lens"), py::arg("n_step"), py::arg("counter"), py::arg("finished"), py::arg("finish_step"),
+        py::arg("done"), py::arg("out"), py::arg("hist"), py::arg("prompt_len"), py::arg("max_new"),
+        py::arg("max_ngram"), py::arg("vocab"), py::arg("plan") = py::none(), py::arg("eos_ids") = py::none());
+  m.def("attn_decode_multi", &attn_decode_multi);
+  m.def("attn_decode_multi_d64", &attn_decode_multi_d64);
   m.def("attn_decode", &attn_decode);
   m.def("attn_decode_d64", &attn_decode_d64);
   m.def("attn_decode_d64_partials", &attn_decode_d64_partials,

@@ -250,10 +250,18 @@ struct AttnDecodeParams {
   const int32_t* seqlens_k;   // valid keys per batch row (may be null: all Sk)
   float scale_log2;           // softmax scale * log2(e)
   float* part_o; float* part_m; float* part_l;  // workspace [B, Hq, NS, (D | 1 | 1)]
+  // attn_decode_multi only: T query tokens per sequence (q / o [B, T, Hq, D], token strides q_ts /
+  // o_ts, o contiguous); the workspace is [B, T, Hq, NS, ...]
+  int T; int64_t q_ts, o_ts;
 };
 int attn_decode_splits(int B, int Hkv, int Sk, int head_dim = 128);
 void attn_decode(const AttnDecodeParams& p, hipStream_t s);
 void attn_decode_d64(const AttnDecodeParams& p, hipStream_t s);
+// verify step of speculative decoding: T in 2..4 query tokens whose keys are the last T of the row;
+// token t attends keys [0, seqlens_k[b] - (T - 1 - t)). Same splits and workspace layout, T times
+// the rows.
+void attn_decode_multi(const AttnDecodeParams& p, hipStream_t s);
+void attn_decode_multi_d64(const AttnDecodeParams& p, hipStream_t s);
 // exact-fp32 variants (attention_f32.hip): same params with fp32 tensors, head_dim 64 or 128
 bool attn_f32_supported(int head_dim);
 void attn_fwd_f32(const AttnParams& p, hipStream_t s);
@@ -436,6 +444,8 @@ struct SampleArgs {
   float mass_scale;   // 2^s, s = min(40, 62 - ceil(log2 V)): V fixed-point masses fit 64 bits
   int64_t seed;
   const int64_t* counter;  // device; null: 0
+  bool candidates;         // logits [T, V] of one sequence: row t draws with counter + t and noise
+                           // row 0, tokens[t] is all that is written (no state tensors)
   uint8_t* keep_mask;      // [B, V] or null (sampling only)
   int64_t* tokens;
   uint8_t* finished;
@@ -449,6 +459,33 @@ struct SampleArgs {
   int64_t out_ld, out_cols;
 };
 void sample_logits(const void* logits, DType dt, const SampleArgs& a, hipStream_t s);
+
+// ---------------- speculative decoding: accept + draft (spec.hip) ----------------
+// One sequence. cand [K + 1] are the sampler's candidates of the verify step whose inputs were
+// ids [K + 1] = [x0, drafts]; semantics in the spec.hip header. Every pointer is device memory.
+constexpr int kSpecMaxDrafts = 3;  // K + 1 <= 4 rows: the limit of the GEMV family
+struct SpecAdvanceArgs {
+  const int64_t* cand;    // [K + 1]
+  int64_t* drafts;        // [K] the drafts as drawn (-1: none); in: this step's, out: the next step's
+  int64_t* ids;           // [K + 1] out: the next step's input ids
+  int32_t* pos;           // [K + 1] positions = cache slots of the inputs
+  int32_t* lens;          // [1] valid keys including the K + 1 inputs
+  int64_t* n_step;        // [1] tokens emitted so far
+  int64_t* counter;       // [1] noise counter of the next token
+  uint8_t* finished;      // [1]
+  int64_t* finish_step;   // [1]
+  uint8_t* done;          // [1] out: finished or n_step >= max_new
+  int64_t* out;           // [>= max_new]
+  int64_t* hist;          // [>= prompt_len + max_new] prompt, then the emitted tokens
+  int64_t prompt_len, max_new;
+  const int64_t* plan;    // null, or [plan_len]: the drafts for token number n are plan[n .. n + K)
+  int64_t plan_len;
+  const int64_t* eos;
+  int n_eos;
+  int K, N;               // drafts per step, longest n-gram of the lookup
+  int64_t vocab;
+};
+void spec_advance(const SpecAdvanceArgs& a, hipStream_t s);
 
 // ---------------- xGMI peer-to-peer collectives (ipc_comm.hip) ----------------
 constexpr int kIpcMaxRanks = 8;

@@ -19,6 +19,10 @@
 //   g_i = -log(-log(u_i))
 // Noise is generated in the final pass only, for kept elements only.
 //
+// Candidate mode (speculative decoding): the rows of logits [T, V] are consecutive tokens of one
+// sequence; row t uses counter + t and noise row 0, i.e. it draws what a one-row call draws at
+// that token number, and only tokens[t] is written.
+//
 // Threshold search: no sort. z maps to a 32-bit key that orders like z; a radix select walks the
 // key in digits of 11 / 11 / 10 bits, one pass over the row (from L2) per digit, each pass filling
 // one LDS histogram with integer atomics: element counts for top-k, and for top-p the masses e_j
@@ -216,8 +220,11 @@ __global__ __launch_bounds__(kNT) void sample_kernel(const T* __restrict__ logit
       tau = radix_select<T, false>(row, V, inv_t, 0.f, 0.f, 0u, (double)a.top_k, 1.0, sh);
     if (live && a.top_p < 1.0)
       tau = radix_select<T, true>(row, V, inv_t, zmax, a.mass_scale, tau, 0.0, a.top_p, sh);
-    const u64 nkey = hash_u64(hash_u64((u64)a.seed) + (a.counter ? (u64)a.counter[0] : 0ull));
-    const u64 rbits = (u64)(uint32_t)row_id << 32;
+    // candidate mode: the rows are consecutive tokens of ONE sequence, so row t draws what the
+    // one-row call draws at counter + t (noise row 0)
+    const u64 ctr = (a.counter ? (u64)a.counter[0] : 0ull) + (a.candidates ? (u64)row_id : 0ull);
+    const u64 nkey = hash_u64(hash_u64((u64)a.seed) + ctr);
+    const u64 rbits = a.candidates ? 0ull : (u64)(uint32_t)row_id << 32;
     uint8_t* mask = a.keep_mask ? a.keep_mask + (int64_t)row_id * V : nullptr;
     for_row(row, V, [&](int i, float x) {
       const float z = scaled(x, inv_t);

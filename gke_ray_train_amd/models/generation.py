@@ -30,6 +30,20 @@ back-to-back replays with no torch op between them and one host read of ``finish
 ``device_loop=False``) restores the host loop, which picks the token with torch ops on the logits
 the graph returns. ``ops/_ref.py::sample_tokens`` is the sampler's host implementation: the same
 logits, seed and counter give the same token on either device.
+
+Prompt-lookup speculative decoding (``generate(..., prompt_lookup_num_tokens=K)``, one sequence)
+replaces the one-token step by a VERIFY step of T = K + 1 tokens: the last emitted token, not yet
+in the cache, and K drafts copied from where the last n-gram occurred before in the prompt and the
+tokens so far. The step is the generic layer step on T rows (``rope_append`` with one position per
+token, the multi-token split-K attention ``attn_decode_multi``, in which token t sees the keys up
+to its own), the LM head on T rows, the sampler's candidate mode (row t draws the token of token
+number n + t) and ``spec_advance`` (csrc/kernels/spec.hip), which keeps the drafts that equal the
+candidates before them, emits 1 .. T tokens, moves positions, valid length and counters on by that
+number and drafts for the next replay — so the loop is still graph replays and one host read per
+``sync_every`` of them. The slots of rejected drafts lie past the valid length and are rewritten by
+the next step; a finished or full row is inert. ``ops/_ref.py::prompt_lookup_draft`` and
+``::spec_accept`` are the host implementations, which the host loops (``device_loop=False``,
+``use_graph=False``) run on the logits [T, V] of the same step.
 """
 from __future__ import annotations
 
@@ -157,8 +171,11 @@ def _mlp(mlp, x):
 
 
 @torch.no_grad()
-def forward_cached(model, ids: torch.Tensor, cache: KVCache, attention_mask=None) -> torch.Tensor:
-    """Run `ids` [B, S] at positions cache.len ... ; returns last-position logits [B, V].
+def forward_cached(model, ids: torch.Tensor, cache: KVCache, attention_mask=None,
+                   all_logits: bool = False) -> torch.Tensor:
+    """Run `ids` [B, S] at positions cache.len ... ; returns last-position logits [B, V], or with
+    ``all_logits`` those of every position [B, S, V] (the verify step of speculative decoding;
+    not with a padded ``attention_mask``).
 
     With a non-trivial ``attention_mask`` [B, S] (prefill of an empty cache only) row b's prompt is
     its masked tokens at positions 0 ... len_b - 1: the rows are compacted to column 0 and run as one
@@ -188,6 +205,11 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache, attention_mask=None
     for li, layer in enumerate(model.model.layers):
         h, residual = _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache, li, row_pos)
     x, _ = ops.add_rms_norm(h, residual, model.model.norm.weight, model.model.norm.eps)
+    if all_logits:
+        if rows is not None or row_pos is not None:
+            raise ValueError("forward_cached: all_logits needs an unpadded, non-ragged cache")
+        cache.len += S
+        return model.lm_head(x).float().view(B, S, -1)
     if rows is not None:
         cache.lens = torch.tensor(rows.lens, dtype=torch.int32, device=ids.device)
         last = x.view(B, S, -1)[torch.arange(B, device=ids.device), cache.lens.long() - 1]
@@ -199,8 +221,10 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache, attention_mask=None
     return model.lm_head(last).float()
 
 
-def _graph_layer_step(layer, h, residual, B, cos, sin, cache: KVCache, li: int, pos_b, pos_l, lens):
-    """One-token layer step with every position-dependent value read from device tensors."""
+def _graph_layer_step(layer, h, residual, B, cos, sin, cache: KVCache, li: int, pos_b, pos_l, lens, T: int = 1):
+    """One-token layer step with every position-dependent value read from device tensors. ``T`` >
+    1 is the verify step of speculative decoding: T tokens per row at positions pos_b [B * T], the
+    last T of the row's ``lens`` valid keys, through the multi-token decode attention."""
     attn = layer.self_attn
     eps = layer.input_layernorm.eps
     if residual is None:
@@ -212,9 +236,12 @@ def _graph_layer_step(layer, h, residual, B, cos, sin, cache: KVCache, li: int, 
     hq, hkv, D = attn.hq, attn.hkv, attn.hd
     # the new token's position is its cache slot, one per row (rows differ after a masked prefill)
     q = _native.kernels().rope_append(qkv.contiguous(), cos, sin, pos_b, hq, hkv, D, cos.shape[0],
-                                      cache.k[li], cache.v[li], 1)
-    o = ops.flash_attention(q.view(B, 1, hq, D), cache.k[li], cache.v[li], causal=False, seqlens_k=lens)
-    h = attn.o_proj(o.reshape(B, hq * D))
+                                      cache.k[li], cache.v[li], T)
+    if T == 1:
+        o = ops.flash_attention(q.view(B, 1, hq, D), cache.k[li], cache.v[li], causal=False, seqlens_k=lens)
+    else:
+        o = ops.decode_attention_multi(q.view(B, T, hq, D), cache.k[li], cache.v[li], seqlens_k=lens)
+    h = attn.o_proj(o.reshape(B * T, hq * D))
     x, residual = ops.add_rms_norm(h, residual, layer.post_attention_layernorm.weight, eps)
     return _mlp(layer.mlp, x), residual
 
@@ -299,6 +326,21 @@ class SamplerConfig:
     pad_id: Optional[int] = None
 
 
+SPEC_MAX_DRAFTS = 3  # kSpecMaxDrafts (csrc/include/grt_kernels.h): K + 1 <= 4 rows, the GEMV family's limit
+
+
+@dataclass
+class SpecConfig:
+    """Prompt-lookup speculative decoding in the captured step: ``num_tokens`` = K drafts per step
+    (1-3), ``max_ngram`` = N, the longest n-gram of the lookup. ``plan`` is a TEST HOOK, not an
+    interface: an int64 device tensor that replaces the lookup, the drafts for token number n
+    being ``plan[n : n + K]`` (-1 past its end). A random-init model never copies its prompt, so
+    this is the one way to exercise acceptance deterministically."""
+    num_tokens: int
+    max_ngram: int = 2
+    plan: Optional[torch.Tensor] = None
+
+
 class GraphDecoder:
     """One-token decode step captured in a HIP graph (see module doc).
 
@@ -311,26 +353,46 @@ class GraphDecoder:
     eagerly, then ``dec.advance()`` per token is nothing but a graph replay. Tokens land in
     ``dec.out[:, n]``, ``dec.finished`` / ``dec.finish_step`` hold the EOS state.
 
+    With ``spec=SpecConfig(K, N)`` (one sequence) the step is the VERIFY step of prompt-lookup
+    speculative decoding: it runs T = K + 1 tokens, the last emitted one and K drafts, and with a
+    sampler ends in the sampler's candidate mode and ``spec_advance`` (csrc/kernels/spec.hip),
+    which accepts the agreeing drafts, emits 1 .. T tokens, moves every position on by that
+    number and drafts for the next replay. ``n_replays`` / ``n_emitted`` count both. Without a
+    sampler ``step_spec(ids, p)`` returns the logits [T, V] and the host does the rest.
+
     Needs a bf16 Llama on the GPU with head_dim 128 or 64 (the HIP RoPE epilogue / decode
     attention kernels)."""
 
-    def __init__(self, model, B: int, max_len: int, sampler: Optional[SamplerConfig] = None):
+    def __init__(self, model, B: int, max_len: int, sampler: Optional[SamplerConfig] = None,
+                 spec: Optional[SpecConfig] = None):
         self.model = model
+        self.spec = spec
+        self.T = 1
+        if spec is not None:
+            if not 1 <= spec.num_tokens <= SPEC_MAX_DRAFTS:
+                raise ValueError(f"SpecConfig.num_tokens must be in 1..{SPEC_MAX_DRAFTS}, got {spec.num_tokens}")
+            if spec.max_ngram < 1:
+                raise ValueError(f"SpecConfig.max_ngram must be >= 1, got {spec.max_ngram}")
+            if B != 1:
+                raise ValueError(f"speculative decoding takes one sequence, got a batch of {B}")
+            self.T = spec.num_tokens + 1
+        T = self.T
+        self.n_replays = 0
         p = next(model.parameters())
         self.device = p.device
         dt = p.dtype if p.dtype in (torch.bfloat16, torch.float32) else torch.bfloat16
         self.cache = KVCache(model.config, B, max_len, self.device, dt)
         self.B = B
         self.cos, self.sin = model.rope(max_len, self.device)
-        self.ids = torch.zeros(B, 1, dtype=torch.long, device=self.device)
-        self.pos_b = torch.zeros(B, dtype=torch.int32, device=self.device)   # RoPE positions
+        self.ids = torch.zeros(B, T, dtype=torch.long, device=self.device)
+        self.pos_b = torch.zeros(B * T, dtype=torch.int32, device=self.device)   # RoPE positions
         self.pos_l = torch.zeros(1, dtype=torch.long, device=self.device)    # cache write index
         self.lens = torch.zeros(B, dtype=torch.int32, device=self.device)    # valid keys incl. new token
         self.graph = None
         self.logits = None
         # residual adds / norms inside the GEMVs when every projection is a plain bf16 Linear
         self.norm_ws = (_NormWorkspace(B, self.device)
-                        if self.device.type == "cuda" and _norm_fusable(model, B) else None)
+                        if self.device.type == "cuda" and spec is None and _norm_fusable(model, B) else None)
         self.sampler = sampler
         if sampler is not None:
             if len(sampler.eos_ids) > SAMPLER_MAX_EOS:
@@ -345,6 +407,34 @@ class GraphDecoder:
             self.out = torch.zeros(B, sampler.max_new_tokens, dtype=torch.long, device=dev)
             self.eos_t = (torch.tensor(sorted(sampler.eos_ids), dtype=torch.long, device=dev)
                           if sampler.eos_ids else None)
+        if spec is not None:
+            dev = self.device
+            self._ar = torch.arange(T, dtype=torch.int32, device=dev)
+            self.cand = torch.zeros(T, dtype=torch.long, device=dev)              # the sampler's candidates
+            self.drafts = torch.full((T - 1,), -1, dtype=torch.long, device=dev)  # as drawn (-1: none)
+            self.done = torch.zeros(1, dtype=torch.bool, device=dev)              # finished or full
+            self.hist = None        # prompt + emitted tokens, allocated by prefill
+            self.prompt_len = 0
+            if spec.plan is not None and (spec.plan.dtype != torch.long or spec.plan.device != dev):
+                raise ValueError("SpecConfig.plan must be an int64 tensor on the model's device")
+
+    @property
+    def n_emitted(self) -> int:
+        """Tokens emitted so far (one host read)."""
+        return int(self.n_step.item())
+
+    def _spec_sample(self, logits: torch.Tensor) -> None:
+        """Candidates of the T logits rows, then accept / emit / advance / draft on the device."""
+        c, K = self.sampler, _native.kernels()
+        if logits.dtype not in (torch.bfloat16, torch.float32):
+            logits = logits.float()
+        rows = logits.shape[0]  # 1 for the prefill logits: only cand[0] is read, no draft can match
+        K.sample_logits(logits, do_sample=c.do_sample, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p,
+                        seed=c.seed, counter=self.counter, next_ids=self.cand[:rows], candidates=True)
+        K.spec_advance(self.cand, self.drafts, self.ids.view(self.T), self.pos_b, self.lens, self.n_step, self.counter,
+                       self.finished, self.finish_step, self.done, self.out.view(-1), self.hist, self.prompt_len,
+                       c.max_new_tokens, self.spec.max_ngram, self.model.config.vocab_size, plan=self.spec.plan,
+                       eos_ids=self.eos_t)
 
     def _sample(self, logits: torch.Tensor) -> None:
         """Pick one token per row with the device sampler and do the loop's bookkeeping: the token
@@ -364,6 +454,9 @@ class GraphDecoder:
     @torch.no_grad()
     def first_token(self, logits: torch.Tensor) -> None:
         """Token 0 from the prefill logits: the captured step's sampler call, run eagerly."""
+        if self.spec is not None:
+            self.drafts.fill_(-1)  # nothing was drafted for the prefill: exactly one token is emitted
+            return self._spec_sample(logits[:1])
         self._sample(logits)
 
     @torch.no_grad()
@@ -371,6 +464,8 @@ class GraphDecoder:
         """Eager prefill. With a padded batch (``attention_mask``, see ``forward_cached``) every
         row then decodes from its own length: the step's position and valid-length tensors differ
         per row, the captured step itself is the same."""
+        if self.spec is not None:
+            return self._spec_prefill(input_ids, attention_mask)
         logits = forward_cached(self.model, input_ids, self.cache, attention_mask)
         n = self.cache.len
         self.pos_l.fill_(n)
@@ -383,9 +478,39 @@ class GraphDecoder:
             self.cache.lens = self.pos_b  # the replays advance it
         return logits
 
+    def _spec_prefill(self, input_ids: torch.Tensor, attention_mask=None) -> torch.Tensor:
+        """Prefill of the one row (a padded row's tokens are compacted as in ``forward_cached``;
+        from then on nothing differs). The positions are left one short of the first verify step's:
+        ``first_token`` emits exactly one token and ``spec_advance`` moves them on by it."""
+        rows = _mask_rows(attention_mask, 1, input_ids.shape[1])
+        prompt = input_ids[0] if rows is None else input_ids[0, rows.start[0]:rows.start[0] + rows.lens[0]]
+        logits = forward_cached(self.model, input_ids, self.cache, rows)
+        n = prompt.shape[0]
+        self.cache.len, self.cache.lens = n, None
+        self.prompt_len = n
+        new = self.sampler.max_new_tokens if self.sampler is not None else 0
+        self.hist = torch.zeros(n + new, dtype=torch.long, device=self.device)
+        self.hist[:n] = prompt
+        self.pos_b.copy_(self._ar + (n - 1))
+        self.lens.fill_(n - 1 + self.T)
+        return logits
+
     @torch.no_grad()
     def _step_body(self):
         m = self.model
+        if self.spec is not None:
+            T = self.T
+            h = m.model.embed_tokens(self.ids).view(T, -1)
+            residual = None
+            for li, layer in enumerate(m.model.layers):
+                h, residual = _graph_layer_step(layer, h, residual, 1, self.cos, self.sin, self.cache, li,
+                                                self.pos_b, self.pos_l, self.lens, T=T)
+            x, _ = ops.add_rms_norm(h, residual, m.model.norm.weight, m.model.norm.eps)
+            logits = m.lm_head(x)  # [T, V]
+            if self.sampler is None:
+                return logits.float()
+            self._spec_sample(logits)  # moves the positions on by the number of tokens emitted
+            return logits
         h = m.model.embed_tokens(self.ids).view(self.B, -1)
         if self.norm_ws is not None:
             for li, layer in enumerate(m.model.layers):
@@ -422,6 +547,8 @@ class GraphDecoder:
         if self.sampler is not None:  # the sampler's epilogue writes these; column n_step of `out`
             # is written again, with the same token, by the first replay
             state += [self.ids, self.finished, self.finish_step, self.n_step, self.counter]
+            if self.spec is not None:  # out / hist past n_step are rewritten alike by the first replay
+                state += [self.drafts, self.done, self.cand]
         saved = [t.clone() for t in state]
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
@@ -442,6 +569,15 @@ class GraphDecoder:
         previous token is already in ``ids``)."""
         if self.sampler is None:
             raise RuntimeError("GraphDecoder.advance() needs a SamplerConfig; use step(next_ids)")
+        if self.spec is not None:
+            # the positions live on the device and a finished or full row is inert: a replay past the
+            # end writes cache slots below prompt + max_new_tokens + K only (generate() sizes the
+            # cache so), and rope_append skips any position outside the cache
+            if self.graph is None:
+                self._capture()
+            self.graph.replay()
+            self.n_replays += 1
+            return
         if self.cache.len >= self.cache.max_len:
             raise RuntimeError("KV cache full")
         if self.graph is None:
@@ -450,9 +586,28 @@ class GraphDecoder:
         self.cache.len += 1
 
     @torch.no_grad()
+    def step_spec(self, ids: torch.Tensor, p: int) -> torch.Tensor:
+        """Host-loop verify step: ``ids`` [T] = the last emitted token and K drafts at positions
+        p ... p + K. Returns the logits [T, V] (the graph's buffer)."""
+        if self.spec is None or self.sampler is not None:
+            raise RuntimeError("GraphDecoder.step_spec() is the sampler-less step of a SpecConfig decoder")
+        if p + self.T > self.cache.max_len:
+            raise RuntimeError("KV cache full")
+        self.ids.copy_(ids.view(1, self.T))
+        self.pos_b.copy_(self._ar + p)
+        self.lens.fill_(p + self.T)
+        if self.graph is None:
+            self._capture()
+        self.graph.replay()
+        self.n_replays += 1
+        return self.logits
+
+    @torch.no_grad()
     def step(self, next_ids: torch.Tensor) -> torch.Tensor:
         if self.sampler is not None:
             raise RuntimeError("GraphDecoder.step() returns logits; with a SamplerConfig use advance()")
+        if self.spec is not None:
+            raise RuntimeError("GraphDecoder.step() takes one token; with a SpecConfig use step_spec(ids, p)")
         if self.cache.len >= self.cache.max_len:
             raise RuntimeError("KV cache full")
         self.ids.copy_(next_ids.view(self.B, 1))
@@ -475,12 +630,82 @@ def _device_loop_ok(graph: bool, generator, n_eos: int, max_new_tokens: int) -> 
             and _native.kernels_available())
 
 
+last_spec_stats = {"n_replays": 0, "n_emitted": 0}  # of the latest speculative generate()
+
+
+def _spec_generate(model, input_ids, rows, P: int, sampler: SamplerConfig, spec: SpecConfig, graph: bool,
+                   on_device: bool, sync_every: int) -> torch.Tensor:
+    """The new tokens [n] of one sequence by prompt-lookup speculative decoding (see ``generate``)."""
+    K, new = spec.num_tokens, sampler.max_new_tokens
+    dev = input_ids.device
+    max_len = P + new + K
+    if on_device:
+        dec = GraphDecoder(model, 1, max_len, sampler=sampler, spec=spec)
+        dec.first_token(dec.prefill(input_ids, rows))
+        left = new - 1  # every replay of a live row emits at least one token
+        while left > 0:
+            chunk = min(sync_every, left)
+            for _i in range(chunk):
+                dec.advance()
+            left -= chunk
+            if left > 0 and bool(dec.done):  # the one host read per chunk: finished or full
+                break
+        n = dec.n_emitted
+        last_spec_stats.update(n_replays=dec.n_replays, n_emitted=n)
+        return dec.out[0, :n]
+    prompt = input_ids[0] if rows is None else input_ids[0, rows.start[0]:rows.start[0] + rows.lens[0]]
+    if graph:
+        dec = GraphDecoder(model, 1, max_len, spec=spec)
+        first = dec.prefill(input_ids, rows)
+
+        def step(ids, p):
+            return dec.step_spec(torch.tensor(ids, device=dev), p)
+    else:
+        pm = next(model.parameters())
+        cache = KVCache(model.config, 1, max_len, dev,
+                        pm.dtype if pm.dtype in (torch.bfloat16, torch.float32) else torch.bfloat16)
+        first = forward_cached(model, input_ids, cache, rows)
+        cache.lens = None  # one row: nothing is ragged once its tokens sit at 0 ... P - 1
+
+        def step(ids, p):
+            cache.len = p  # the slots of rejected drafts are rewritten
+            return forward_cached(model, torch.tensor([ids], device=dev), cache, all_logits=True)[0]
+
+    def pick(logits, n):  # the sampler's host implementation, row t at token number n + t
+        if not sampler.do_sample:
+            return logits.argmax(-1).tolist()
+        return [int(_ref.sample_tokens(logits[t:t + 1], seed=sampler.seed, counter=n + t, temperature=sampler.temperature,
+                                       top_k=sampler.top_k, top_p=sampler.top_p)) for t in range(logits.shape[0])]
+
+    V = model.config.vocab_size
+    plan = spec.plan.tolist() if spec.plan is not None else None
+    hist = prompt.tolist()
+    out, fin, _ = _ref.spec_accept([-1] * K, pick(first[:1], 0), 0, new, sampler.eos_ids)
+    hist += out
+    replays = 0
+    while not fin and len(out) < new:
+        n = len(out)
+        if plan is not None:
+            drafts = (plan[n:n + K] + [-1] * K)[:K]
+        else:
+            drafts = _ref.prompt_lookup_draft(hist, len(hist), K, spec.max_ngram)
+        ids = [hist[-1]] + [d if 0 <= d < V else 0 for d in drafts]
+        logits = step(ids, P + n - 1)
+        emitted, fin, _ = _ref.spec_accept(drafts, pick(logits, n), n, new, sampler.eos_ids)
+        out += emitted
+        hist += emitted
+        replays += 1
+    last_spec_stats.update(n_replays=replays, n_emitted=len(out))
+    return torch.tensor(out, dtype=torch.long, device=dev)
+
+
 @torch.no_grad()
 def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              eos_token_id: Optional[Union[int, List[int]]] = None, do_sample: bool = False, temperature: float = 1.0,
              top_p: Optional[float] = None, attention_mask=None, pad_token_id=None, generator=None,
              use_graph: Optional[bool] = None, sync_every: int = 16, top_k: Optional[int] = None,
-             seed: Optional[int] = None, device_loop: Optional[bool] = None, **_):
+             seed: Optional[int] = None, device_loop: Optional[bool] = None,
+             prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: int = 2, _spec_plan=None, **_):
     """Returns [B, prompt + generated] token ids (HF ``generate`` output convention).
 
     ``attention_mask`` [B, S] (bool / integer, HF semantics) batches prompts of unequal length: row
@@ -508,7 +733,24 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     On the graph path with no ``generator`` and at most 8 EOS ids, the token is picked inside the
     captured step by the device sampler (``device_loop``, default on; ``GRT_DEVICE_SAMPLER=0`` or
     ``device_loop=False`` restore the host loop): the loop is graph replays and one host read of
-    ``finished.all()`` every ``sync_every`` tokens."""
+    ``finished.all()`` every ``sync_every`` tokens.
+
+    ``prompt_lookup_num_tokens`` = K in 1..3 (None / 0: off, the default) with
+    ``max_matching_ngram_size`` = N (HF's names; N defaults to 2) turns on prompt-lookup
+    speculative decoding for ONE sequence: every step drafts K tokens by looking the last n <= N
+    tokens up in the prompt and the tokens so far (``_ref.prompt_lookup_draft``), runs the last
+    token and the drafts as one T = K + 1 row verify step, and keeps the drafts that equal the
+    token the sampler draws at their token number, plus one (``_ref.spec_accept``). Because the
+    sampler's noise depends on the token number alone, that rule is exact for greedy and for
+    ``do_sample=True``: the output is what the same call gives without drafts, up to near-ties in
+    the logits, which the 1-row and the T-row kernels may round differently. The cache holds
+    prompt + ``max_new_tokens`` + K positions. Every decode path takes it: on the graph path with
+    the device loop the draft, the candidates and the accept step run inside the captured step
+    (csrc/kernels/spec.hip) and the host reads one "finished or full" flag every ``sync_every``
+    replays; the graph host loop and the eager path do them on the host. ``ValueError``: K outside
+    1..3, N < 1, more than one sequence, a ``generator``, or prompt + ``max_new_tokens`` + K past
+    ``max_position_embeddings``. ``_spec_plan`` is a private test hook (``SpecConfig.plan``).
+    ``last_spec_stats`` holds the verify steps and tokens of the latest such call."""
     was = model.training
     model.eval()
     B, S = input_ids.shape
@@ -529,6 +771,32 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     if device_loop and not can:
         raise ValueError("generate: device_loop=True needs the graph path (bf16 model on the GPU, native kernels), "
                          f"no generator, at most {SAMPLER_MAX_EOS} EOS ids and max_new_tokens >= 1")
+    K = int(prompt_lookup_num_tokens or 0)
+    if K:
+        N = int(max_matching_ngram_size)
+        limit = model.config.max_position_embeddings
+        if not 1 <= K <= SPEC_MAX_DRAFTS:
+            raise ValueError(f"generate: prompt_lookup_num_tokens must be in 1..{SPEC_MAX_DRAFTS} (the verify step runs "
+                             f"K + 1 <= {SPEC_MAX_DRAFTS + 1} rows, the limit of the GEMV kernels), got {K}")
+        if N < 1:
+            raise ValueError(f"generate: max_matching_ngram_size must be >= 1, got {N}")
+        if B != 1:
+            raise ValueError(f"generate: prompt lookup decoding takes a batch of 1, got {B} sequences")
+        if generator is not None:
+            raise ValueError("generate: prompt lookup decoding needs the counter-based noise (seed=...), not a "
+                             "torch generator: a draft is accepted iff it is the token drawn at its token number")
+        if P + max_new_tokens + K > limit:
+            raise ValueError(f"generate: prompt ({P}) + max_new_tokens ({max_new_tokens}) + prompt_lookup_num_tokens "
+                             f"({K}) exceeds max_position_embeddings ({limit}), the extent of the RoPE table")
+    if K and max_new_tokens >= 1:
+        sampler = SamplerConfig(max_new_tokens=max_new_tokens, do_sample=do_sample, temperature=temperature, top_k=top_k,
+                                top_p=top_p, seed=seed, eos_ids=tuple(sorted(eos)), pad_id=pad_token_id)
+        spec = SpecConfig(K, N, _spec_plan)
+        on_device = can and (device_loop if device_loop is not None else _DEVICE_SAMPLER)
+        new = _spec_generate(model, input_ids, rows, P, sampler, spec, graph, on_device, sync_every)
+        if was:
+            model.train()
+        return torch.cat([input_ids, new[None]], 1)
     if can and (device_loop if device_loop is not None else _DEVICE_SAMPLER):
         cfg = SamplerConfig(max_new_tokens=max_new_tokens, do_sample=do_sample, temperature=temperature, top_k=top_k,
                             top_p=top_p, seed=seed, eos_ids=tuple(sorted(eos)), pad_id=pad_token_id)

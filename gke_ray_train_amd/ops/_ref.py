@@ -385,3 +385,46 @@ def adamw8_(p, g, codes_m, absmax_m, codes_v, absmax_v, step, lr, beta1, beta2, 
         c, a = quantize_blockwise8(x, signed)
         codes.copy_(c)
         absmax.copy_(a)
+
+
+# ----------------------------------------------------------------------------- prompt-lookup speculative decoding
+# Host implementations (and oracles) of the draft and accept steps of csrc/kernels/spec.hip. All
+# of it is integer work, so the kernels give the same values bit for bit.
+def prompt_lookup_draft(hist, n_hist: int, K: int, N: int):
+    """K draft tokens for the sequence ``hist[:n_hist]`` (prompt + tokens emitted so far; any
+    sequence of ints or a 1-D tensor). For n = min(N, n_hist - 1) down to 1, the last n tokens are
+    searched among the earlier positions: an occurrence starting at s counts when its continuation
+    holds at least one token (s + n < n_hist; it may overlap the suffix), and the latest one wins.
+    The draft is hist[s + n : s + n + K], cut at the end of the history; unfilled slots, and every
+    slot when no n matches, are -1, which equals no token."""
+    h = hist.tolist() if hasattr(hist, "tolist") else list(hist)
+    for n in range(min(N, n_hist - 1), 0, -1):
+        tail = h[n_hist - n:n_hist]
+        for s in range(n_hist - n - 1, -1, -1):
+            if h[s:s + n] == tail:
+                d = h[s + n:min(s + n + K, n_hist)]
+                return d + [-1] * (K - len(d))
+    return [-1] * K
+
+
+def spec_accept(drafts, cand, n: int, max_new_tokens: int, eos_ids=(), finished: bool = False):
+    """The accept step of one verify pass. ``cand[t]`` is the token the sampler draws from logits
+    row t (token number n + t), ``drafts[i]`` the draft that was fed as input i + 1, ``n`` the
+    number of tokens emitted so far. The accepted count a is the largest j with drafts[i] ==
+    cand[i] for all i < j; cand[0 .. a] are emitted, cut after the first EOS among them and at
+    ``max_new_tokens``. Returns (emitted, finished, finish_step): ``finish_step`` is the token
+    number of the EOS when this step finished the row, else -1. A row that is finished or full
+    (n >= max_new_tokens) is inert: nothing is emitted."""
+    if finished or n >= max_new_tokens:
+        return [], bool(finished), -1
+    a = 0
+    while a < len(drafts) and int(drafts[a]) == int(cand[a]):
+        a += 1
+    out = []
+    for i in range(a + 1):
+        if n + len(out) >= max_new_tokens:
+            break
+        out.append(int(cand[i]))
+        if out[-1] in eos_ids:
+            return out, True, n + len(out) - 1
+    return out, False, -1

@@ -289,6 +289,26 @@ def flash_attention(q, k, v, causal=True, scale=None, seqlens_k=None, dropout_p=
     return _ref.attention(q, k, v, causal=causal, scale=scale, seqlens_k=seqlens_k, dropout_p=dropout_p, seed=seed)
 
 
+def decode_attention_multi(q, k, v, seqlens_k=None, scale=None):
+    """The verify step of speculative decoding: q [B, T, Hq, D] are T = 2..4 new tokens per row
+    whose keys are the last T valid ones of k / v [B, Sk, Hkv, D] (any strides); ``seqlens_k`` [B]
+    int32 counts the valid keys including them (None: Sk). Token t attends keys
+    [0, seqlens_k[b] - (T - 1 - t)). bf16 on the GPU with head_dim 128 or 64: the split-K kernel
+    that loads every K / V element once for all T tokens of a GQA group (decode_attention.hip);
+    anything else on the GPU is an error, not a slower path. The CPU takes the fp32 math path."""
+    B, T, Hq, D = q.shape
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if _gpu(q):
+        C = _native.kernels()
+        if D not in (64, 128):
+            raise ValueError(f"decode_attention_multi: no gfx950 kernel for head_dim {D} (64 or 128)")
+        return (C.attn_decode_multi if D == 128 else C.attn_decode_multi_d64)(q, k, v, seqlens_k, scale)
+    lens = seqlens_k.long() if seqlens_k is not None else torch.full((B,), k.shape[1], dtype=torch.long)
+    out = [_ref.attention(q[:, t:t + 1], k, v, causal=False, scale=scale, seqlens_k=lens - (T - 1 - t))
+           for t in range(T)]
+    return torch.cat(out, 1)
+
+
 _warned = set()
 
 

@@ -9,7 +9,13 @@ on and off, the arms alternating ``DECODE_ROUNDS`` (2) times in this one process
 keeps one cache mode (70B: 0); ``DECODE_B`` may be a comma list here.
 
 ``DECODE_SAMPLE=greedy|top_p`` and / or ``DECODE_DEVICE_LOOP=0|1`` times the HIP-graph decoder with the
-token picked on the device inside the captured step against the host loop (``sampler_main``)."""
+token picked on the device inside the captured step against the host loop (``sampler_main``).
+
+``DECODE_SPEC=K`` (a comma list of 1-3) times prompt-lookup speculative decoding (``generate(...,
+prompt_lookup_num_tokens=K)``, device loop) against the plain device loop (``spec_main``).
+
+``DECODE_ATTN=1`` times the multi-token decode attention kernel alone against T launches of the
+one-token kernel (``attn_main``)."""
 import json
 import os
 import sys
@@ -105,8 +111,101 @@ def sampler_main():
                               "ms_per_token": round(step * 1e3, 3)}), flush=True)
 
 
+def spec_main():
+    """``DECODE_SPEC=K[,K...]``: greedy, batch 1, prompt 512, ``DECODE_NEW`` (128) tokens. The drafts
+    come from the test hook ``_spec_plan`` so that the acceptance is forced: the run's own tokens
+    (100 %: every verify step emits K + 1 tokens), the same with every second token wrong (50 %)
+    and with every token wrong (0 %: every step emits 1 token, so its time is the verify step's).
+    The plain device loop and the speculative arms alternate ``DECODE_ROUNDS`` (2) times in this one
+    process. ``ms_per_step`` is per graph replay; the replays include those past the last token up
+    to the next host read (``sync_every`` 16), which emit nothing and cost a step each."""
+    from gke_ray_train_amd.models import generation as G
+    ks = [int(k) for k in os.environ["DECODE_SPEC"].split(",")]
+    new = int(os.environ.get("DECODE_NEW", "128"))
+    net = build_llama(model, device="cuda", dtype=torch.bfloat16, seed=0).eval()
+    V = net.config.vocab_size
+    ids = torch.randint(0, V, (1, 512), device="cuda")
+    plain = net.generate(ids, max_new_tokens=new, use_graph=True)[0, 512:]
+    arms = [("plain", 0, None, plain)]
+    for K in ks:
+        # A random-init model's logits are nearly flat, so the verify step (norms outside the GEMVs,
+        # K + 1 rows) soon picks other tokens than the plain step: the plan that is accepted in full
+        # is the speculative run's own output, found by feeding it back until it reproduces itself.
+        plan = plain
+        for _ in range(4):
+            out = net.generate(ids, max_new_tokens=new, use_graph=True, prompt_lookup_num_tokens=K, _spec_plan=plan)
+            if torch.equal(out[0, 512:], plan):
+                break
+            plan = out[0, 512:].clone()
+        wrong = (plan + 1) % V
+        half = torch.where(torch.arange(new, device="cuda") % 2 == 1, wrong, plan)
+        arms += [(f"spec_{pct}", K, p, plan) for pct, p in (("100", plan), ("50", half), ("0", wrong))]
+    for rnd in range(int(os.environ.get("DECODE_ROUNDS", "2"))):
+        for name, K, plan, ref in arms:
+            kw = dict(prompt_lookup_num_tokens=K, _spec_plan=plan) if K else {}
+            net.generate(ids, max_new_tokens=8, use_graph=True, **kw)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            net.generate(ids, max_new_tokens=2, use_graph=True, **kw)  # prefill, capture, one replay
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            out = net.generate(ids, max_new_tokens=new, use_graph=True, **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t1
+            n = out.shape[1] - 512
+            replays = G.last_spec_stats["n_replays"] if K else n - 1
+            same = int((out[0, 512:] == ref[:n]).sum())  # whatever the drafts, the tokens stay the same
+            print(json.dumps({"model": model, "arm": name, "K": K, "round": rnd, "new_tokens": n, "replays": replays,
+                              "tokens_as_without_drafts": same, "seconds": round(dt, 3),
+                              "tokens_per_s": round(n / dt, 1),
+                              "ms_per_step": round((dt - (t1 - t0)) / max(replays - 1, 1) * 1e3, 3),
+                              "decode_tokens_per_s": round((n - 2) / (dt - (t1 - t0)), 1)}), flush=True)
+
+
+def attn_main():
+    """``DECODE_ATTN=1``: ``attn_decode_multi`` at T = 2, 3, 4 against T launches of ``attn_decode``
+    (what verifying token by token costs), batch 1, 32 query / 8 kv heads, head_dim 128 and 64, a
+    cache of 640 slots with 600 valid keys. Back-to-back launches timed with events, the two arms
+    alternating ``DECODE_ROUNDS`` (3) times."""
+    from gke_ray_train_amd import _native
+    C = _native.kernels()
+    iters = 300
+
+    def timed(fn):
+        for _ in range(20):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / iters * 1e3
+
+    for D in (128, 64):
+        multi = C.attn_decode_multi if D == 128 else C.attn_decode_multi_d64
+        one = C.attn_decode if D == 128 else C.attn_decode_d64
+        k = torch.randn(1, 640, 8, D, device="cuda", dtype=torch.bfloat16)
+        v = torch.randn(1, 640, 8, D, device="cuda", dtype=torch.bfloat16)
+        sl = torch.tensor([600], device="cuda", dtype=torch.int32)
+        for T in (2, 3, 4):
+            q = torch.randn(1, T, 32, D, device="cuda", dtype=torch.bfloat16)
+            qs = [q[:, t:t + 1] for t in range(T)]
+            for rnd in range(int(os.environ.get("DECODE_ROUNDS", "3"))):
+                us_m = timed(lambda: multi(q, k, v, sl, D ** -0.5))
+                us_1 = timed(lambda: [one(x, k, v, sl, D ** -0.5) for x in qs])
+                print(json.dumps({"kernel": "attn_decode_multi", "head_dim": D, "T": T, "round": rnd,
+                                  "multi_us": round(us_m, 2), "T_single_launches_us": round(us_1, 2)}), flush=True)
+
+
 if QUANT:
     nf4_main()
+    sys.exit(0)
+if "DECODE_SPEC" in os.environ:
+    spec_main()
+    sys.exit(0)
+if "DECODE_ATTN" in os.environ:
+    attn_main()
     sys.exit(0)
 if "DECODE_SAMPLE" in os.environ or "DECODE_DEVICE_LOOP" in os.environ:
     sampler_main()
