@@ -1068,7 +1068,7 @@ void rope_attn_bwd_d64(const Tensor& dout, const Tensor& qkv, const Tensor& cos,
 }
 
 // Split-K decode attention (decode_attention.hip). D is the binding's head dim: attn_decode is the
-// head_dim-128 entry point and refuses anything else, attn_decode_d64 the head_dim-64 one.
+// head_dim-128 binding and refuses anything else, attn_decode_d64 the head_dim-64 one; multi: T 2..4.
 Tensor attn_decode_impl(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& seqlens_k,
                         double scale, int64_t D, const char* op, std::vector<Tensor>* partials = nullptr,
                         bool multi = false) {
@@ -1124,11 +1124,7 @@ Tensor attn_decode_impl(const Tensor& q, const Tensor& k, const Tensor& v, const
   p.part_o = ws.data_ptr<float>();
   p.part_m = p.part_o + rows * p.NS * D;
   p.part_l = p.part_m + rows * p.NS;
-  if (multi) {
-    if (D == 64) grt::attn_decode_multi_d64(p, cur_stream(q));
-    else grt::attn_decode_multi(p, cur_stream(q));
-  } else if (D == 64) grt::attn_decode_d64(p, cur_stream(q));
-  else grt::attn_decode(p, cur_stream(q));
+  grt::attn_decode(p, (int)D, cur_stream(q));
   if (partials) {
     const int64_t n = rows * p.NS;
     *partials = {ws.narrow(0, 0, n * D).view({p.B, Hq, p.NS, D}), ws.narrow(0, n * D, n).view({p.B, Hq, p.NS}),

@@ -240,28 +240,24 @@ struct AttnBwdParams {
 };
 void attn_bwd(const AttnBwdParams& p, hipStream_t s);
 int64_t attn_bwd_workspace_floats(int B, int Hq, int Sq, int D);
-// decode (Sq = 1) split-K attention (decode_attention.hip): bf16, Hq / Hkv in {1,2,4,8}; head_dim 128
-// (attn_decode) or 64 (attn_decode_d64), NS = attn_decode_splits(.., head_dim), workspace
-// B * Hq * NS * (head_dim + 2) floats (unused at head_dim 64 when NS == 1: one launch, no combine)
+// decode split-K attention (decode_attention.hip): bf16, Hq / Hkv in {1,2,4,8}, head_dim 128 or 64,
+// T = 1 query token per sequence (the decode step) or T in 2..4 whose keys are the last T of the row
+// (verify step of speculative decoding): token t attends keys [0, seqlens_k[b] - (T - 1 - t)).
+// NS = attn_decode_splits(.., head_dim), workspace B * T * Hq * NS * (head_dim + 2) floats (unused
+// at head_dim 64 when NS == 1: one launch, no combine)
 struct AttnDecodeParams {
   const void* q; const void* k; const void* v; void* o;
   int64_t q_bs, q_hs, k_bs, k_ss, k_hs, v_bs, v_ss, v_hs, o_bs, o_hs;
   int B, Hq, Hkv, Sk, NS;
   const int32_t* seqlens_k;   // valid keys per batch row (may be null: all Sk)
   float scale_log2;           // softmax scale * log2(e)
-  float* part_o; float* part_m; float* part_l;  // workspace [B, Hq, NS, (D | 1 | 1)]
-  // attn_decode_multi only: T query tokens per sequence (q / o [B, T, Hq, D], token strides q_ts /
-  // o_ts, o contiguous); the workspace is [B, T, Hq, NS, ...]
+  float* part_o; float* part_m; float* part_l;  // workspace [B, T, Hq, NS, (D | 1 | 1)]
+  // T query tokens per sequence, always set: q / o are [B, T, Hq, D] with token strides q_ts /
+  // o_ts, o contiguous
   int T; int64_t q_ts, o_ts;
 };
 int attn_decode_splits(int B, int Hkv, int Sk, int head_dim = 128);
-void attn_decode(const AttnDecodeParams& p, hipStream_t s);
-void attn_decode_d64(const AttnDecodeParams& p, hipStream_t s);
-// verify step of speculative decoding: T in 2..4 query tokens whose keys are the last T of the row;
-// token t attends keys [0, seqlens_k[b] - (T - 1 - t)). Same splits and workspace layout, T times
-// the rows.
-void attn_decode_multi(const AttnDecodeParams& p, hipStream_t s);
-void attn_decode_multi_d64(const AttnDecodeParams& p, hipStream_t s);
+void attn_decode(const AttnDecodeParams& p, int head_dim, hipStream_t s);
 // exact-fp32 variants (attention_f32.hip): same params with fp32 tensors, head_dim 64 or 128
 bool attn_f32_supported(int head_dim);
 void attn_fwd_f32(const AttnParams& p, hipStream_t s);

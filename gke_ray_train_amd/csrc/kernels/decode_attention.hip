@@ -1,4 +1,5 @@
-// Split-K attention for the decode step (one new query token per sequence), bf16, head_dim 128 or 64.
+// Split-K attention for the decode step, bf16, head_dim 128 or 64: one new query token per sequence,
+// or the 2-4 query tokens of a speculative verify step.
 //
 // Reference role: the KV-cache decode of HF ``generate`` in the inference comparison
 // (reference ray-jobs/fine_tune_llama_ray.py:138-146). With Sq = 1 the
@@ -18,22 +19,35 @@
 // (Sk <= kSingleSplitKeys) is one split that writes the output itself: below that length the
 // second launch costs more than the splits save.
 //
-// attn_decode_multi (further down) is the same kernel for the 2-4 query tokens of a speculative
-// verify step.
+// The split kernel is also a template on TT, the query tokens a workgroup handles. TT = 1 is the
+// decode step. The verify step of speculative decoding has T = 2..4 query tokens per sequence, the
+// last T keys of the row being their own: query token t of row b attends keys
+// [0, len_b - (T - 1 - t)), len_b the valid keys including all T new ones. Split plan, lane mapping
+// and partial-state contract are the same (the splits cover [0, len_b)); a workgroup keeps
+// R = G * TT query rows in registers (TT tokens of the GQA group), so every K / V element is loaded
+// once for all of them, and a row skips the keys at or past its own length. TT = T up to R = 16
+// rows (q and o are 8 fp32 registers per row each); G = 8 with T = 3 or 4 would need 24 / 32 rows,
+// more than the 512-register file of a 256-thread workgroup holds without scratch, so those two
+// cases run TT = 2 tokens per workgroup and tile the tokens over blockIdx.z (K / V are then read
+// twice). Partials are [B, T, Hq, NS].
 #include "grt_common.h"
 #include "grt_kernels.h"
 
 namespace grt {
 namespace {
 
-template <int D, int G>
+// Everything that exists only for TT > 1 (token tile, per-row key limit, token terms of the
+// addresses) is behind the compile-time TT, so TT = 1 carries none of it.
+template <int D, int G, int TT>
 __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecodeParams p) {
   constexpr int kLanes = D / 8;           // lanes per key
   constexpr int kWaveKeys = 64 / kLanes;  // keys per wave per step
   constexpr int kStep = 4 * kWaveKeys;    // keys per workgroup per step
-  __shared__ float sm_m[4][G], sm_l[4][G];
-  __shared__ float sm_o[4][G][D];
+  constexpr int R = G * TT;  // row r: token t0 + r / G, query head hkv * G + r % G
+  __shared__ float sm_m[4][R], sm_l[4][R];
+  __shared__ float sm_o[4][R][D];
   const int bh = blockIdx.x, split = blockIdx.y;
+  const int t0 = TT > 1 ? blockIdx.z * TT : 0;
   const int b = bh / p.Hkv, hkv = bh % p.Hkv;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int grp = lane / kLanes, c = lane % kLanes;  // key lane-group, 16-byte chunk of the head dim
@@ -52,21 +66,26 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
     kraw = *reinterpret_cast<const u32x4*>(Kb + (int64_t)j * p.k_ss);
     vraw = *reinterpret_cast<const u32x4*>(Vb + (int64_t)j * p.v_ss);
   }
-  float q[G][8];
+  float q[R][8];
+  int rlen[TT];  // TT > 1: keys token t0 + tt sees; 0 for a token past T (last tile of an uneven tiling)
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const bf16* qp = (const bf16*)p.q + (int64_t)b * p.q_bs + (int64_t)(hkv * G + g) * p.q_hs + c * 8;
-    bf16x8_to_f32(*reinterpret_cast<const u32x4*>(qp), q[g]);
+  for (int tt = 0; tt < TT; ++tt) rlen[tt] = t0 + tt < p.T ? len - (p.T - 1 - (t0 + tt)) : 0;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) q[g][i] *= p.scale_log2;  // scores in log2 units
+  for (int r = 0; r < R; ++r) {
+    const int t = TT > 1 ? min(t0 + r / G, p.T - 1) : 0;  // a token past T reads token T - 1's q and uses none of it
+    const bf16* qp = (const bf16*)p.q + (int64_t)b * p.q_bs + (int64_t)t * p.q_ts +
+                     (int64_t)(hkv * G + r % G) * p.q_hs + c * 8;
+    bf16x8_to_f32(*reinterpret_cast<const u32x4*>(qp), q[r]);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) q[r][i] *= p.scale_log2;  // scores in log2 units
   }
-  float m[G], l[G], o[G][8];
+  float m[R], l[R], o[R][8];
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    m[g] = -INFINITY;
-    l[g] = 0.f;
+  for (int r = 0; r < R; ++r) {
+    m[r] = -INFINITY;
+    l[r] = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o[g][i] = 0.f;
+    for (int i = 0; i < 8; ++i) o[r][i] = 0.f;
   }
   for (; j < k1; j += kStep) {
     float kf[8], vf[8];
@@ -77,62 +96,70 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
       vraw = *reinterpret_cast<const u32x4*>(Vb + (int64_t)(j + kStep) * p.v_ss);
     }
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
+    for (int r = 0; r < R; ++r) {
       float s = 0.f;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) s = fmaf(q[g][i], kf[i], s);
+      for (int i = 0; i < 8; ++i) s = fmaf(q[r][i], kf[i], s);
 #pragma unroll
       for (int off = kLanes / 2; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-      const float mn = fmaxf(m[g], s);
-      const float a = fast_exp2(m[g] - mn), e = fast_exp2(s - mn);
-      l[g] = l[g] * a + e;
+      // one token sees every key of its split; the limit of a row of several is uniform over the
+      // lanes of a key, and the shuffles above stay outside it
+      if (TT == 1 || j < rlen[r / G]) {
+        const float mn = fmaxf(m[r], s);
+        const float a = fast_exp2(m[r] - mn), e = fast_exp2(s - mn);
+        l[r] = l[r] * a + e;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[g][i] = fmaf(o[g][i], a, e * vf[i]);
-      m[g] = mn;
+        for (int i = 0; i < 8; ++i) o[r][i] = fmaf(o[r][i], a, e * vf[i]);
+        m[r] = mn;
+      }
     }
   }
   // merge the key lane-groups of the wave (lanes c, c + D/8, c + 2 D/8, ... hold the same dims)
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
+  for (int r = 0; r < R; ++r) {
 #pragma unroll
     for (int off = kLanes; off <= 32; off <<= 1) {
-      const float m2 = __shfl_xor(m[g], off, 64), l2 = __shfl_xor(l[g], off, 64);
-      const float mn = fmaxf(m[g], m2);
-      const float a = mn == -INFINITY ? 0.f : fast_exp2(m[g] - mn);
+      const float m2 = __shfl_xor(m[r], off, 64), l2 = __shfl_xor(l[r], off, 64);
+      const float mn = fmaxf(m[r], m2);
+      const float a = mn == -INFINITY ? 0.f : fast_exp2(m[r] - mn);
       const float a2 = mn == -INFINITY ? 0.f : fast_exp2(m2 - mn);
-      l[g] = l[g] * a + l2 * a2;
+      l[r] = l[r] * a + l2 * a2;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[g][i] = o[g][i] * a + __shfl_xor(o[g][i], off, 64) * a2;
-      m[g] = mn;
+      for (int i = 0; i < 8; ++i) o[r][i] = o[r][i] * a + __shfl_xor(o[r][i], off, 64) * a2;
+      m[r] = mn;
     }
     if (grp == 0) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) sm_o[wave][g][c * 8 + i] = o[g][i];
-      if (c == 0) { sm_m[wave][g] = m[g]; sm_l[wave][g] = l[g]; }
+      for (int i = 0; i < 8; ++i) sm_o[wave][r][c * 8 + i] = o[r][i];
+      if (c == 0) { sm_m[wave][r] = m[r]; sm_l[wave][r] = l[r]; }
     }
   }
   __syncthreads();
-  // merge the 4 waves: thread t handles (g, d) pairs
-  for (int idx = threadIdx.x; idx < G * D; idx += 256) {
-    const int g = idx / D, d = idx % D;
+  // merge the 4 waves: thread t handles (r, d) pairs
+  for (int idx = threadIdx.x; idx < R * D; idx += 256) {
+    const int r = idx / D, d = idx % D;
+    const int t = TT > 1 ? t0 + r / G : 0, hq = hkv * G + (TT > 1 ? r % G : r);
+    if (TT > 1 && t >= p.T) continue;
     float mm = -INFINITY;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) mm = fmaxf(mm, sm_m[w][g]);
+    for (int w = 0; w < 4; ++w) mm = fmaxf(mm, sm_m[w][r]);
     float ll = 0.f, oo = 0.f;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
-      const float a = mm == -INFINITY ? 0.f : fast_exp2(sm_m[w][g] - mm);
-      ll += sm_l[w][g] * a;
-      oo += sm_o[w][g][d] * a;
+      const float a = mm == -INFINITY ? 0.f : fast_exp2(sm_m[w][r] - mm);
+      ll += sm_l[w][r] * a;
+      oo += sm_o[w][r][d] * a;
     }
     if constexpr (D == 64) {
       if (p.NS == 1) {  // short cache, one split: this is the whole softmax, no combine launch
-        bf16* op = (bf16*)p.o + (int64_t)b * p.o_bs + (int64_t)(hkv * G + g) * p.o_hs + d;
+        bf16* op = (bf16*)p.o + (int64_t)b * p.o_bs + (int64_t)t * p.o_ts + (int64_t)hq * p.o_hs + d;
         *op = static_cast<bf16>(ll > 0.f ? oo / ll : 0.f);
         continue;
       }
     }
-    const int64_t slot = ((int64_t)(b * p.Hq + hkv * G + g) * p.NS + split);
+    // partials [B, T, Hq, NS]; one token keeps its 32-bit row index
+    const int64_t slot = TT > 1 ? ((int64_t)(b * p.T + t) * p.Hq + hq) * p.NS + split
+                                : (int64_t)(b * p.Hq + hkv * G + r) * p.NS + split;
     p.part_o[slot * D + d] = oo;
     if (d == 0) { p.part_m[slot] = mm; p.part_l[slot] = ll; }
   }
@@ -174,177 +201,35 @@ __global__ __launch_bounds__(D) void attn_decode_combine_kernel(const AttnDecode
   *op = static_cast<bf16>(ll > 0.f ? oo / ll : 0.f);
 }
 
-template <int D>
-void launch_decode(const AttnDecodeParams& p, hipStream_t s) {
-  const dim3 g1((unsigned)(p.B * p.Hkv), (unsigned)p.NS);
-  const int G = p.Hq / p.Hkv;
-  switch (G) {
-    case 1: hipLaunchKernelGGL((attn_decode_split_kernel<D, 1>), g1, dim3(256), 0, s, p); break;
-    case 2: hipLaunchKernelGGL((attn_decode_split_kernel<D, 2>), g1, dim3(256), 0, s, p); break;
-    case 4: hipLaunchKernelGGL((attn_decode_split_kernel<D, 4>), g1, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL((attn_decode_split_kernel<D, 8>), g1, dim3(256), 0, s, p); break;
-  }
-  if (D == 64 && p.NS == 1) return;  // the split kernel wrote the output itself
-  hipLaunchKernelGGL(attn_decode_combine_kernel<D>, dim3((unsigned)(p.B * p.Hq)), dim3(D), 0, s, p);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Verify step of speculative decoding: T = 2..4 query tokens per sequence, the last T keys of the
-// row being their own. Query token t of row b attends keys [0, len_b - (T - 1 - t)), len_b the
-// valid keys including all T new ones. Same split plan, lane mapping and partial-state contract as
-// the one-token kernel above (the splits cover [0, len_b)); the difference is that a workgroup
-// keeps R = G * TT query rows in registers (TT tokens of the GQA group), so every K / V element is
-// loaded once for all of them, and that a row skips the keys at or past its own length. TT = T up
-// to R = 16 rows (q and o are 8 fp32 registers per row each); G = 8 with T = 3 or 4 would need 24 /
-// 32 rows, more than the 512-register file of a 256-thread workgroup holds without scratch, so
-// those two cases run TT = 2 tokens per workgroup and tile the tokens over blockIdx.z (K / V are
-// then read twice). Partials are [B, T, Hq, NS].
 template <int D, int G, int TT>
-__global__ __launch_bounds__(256) void attn_decode_multi_split_kernel(const AttnDecodeParams p) {
-  constexpr int kLanes = D / 8;
-  constexpr int kWaveKeys = 64 / kLanes;
-  constexpr int kStep = 4 * kWaveKeys;
-  constexpr int R = G * TT;  // row r: token t0 + r / G, query head hkv * G + r % G
-  __shared__ float sm_m[4][R], sm_l[4][R];
-  __shared__ float sm_o[4][R][D];
-  const int bh = blockIdx.x, split = blockIdx.y;
-  const int t0 = blockIdx.z * TT;
-  const int b = bh / p.Hkv, hkv = bh % p.Hkv;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int grp = lane / kLanes, c = lane % kLanes;
-  int len = p.Sk;
-  if (p.seqlens_k) len = min(len, p.seqlens_k[b]);
-  const int per = ((len + p.NS - 1) / p.NS + kStep - 1) / kStep * kStep;
-  const int k0 = split * per, k1 = min(len, k0 + per);
-
-  const bf16* Kb = (const bf16*)p.k + (int64_t)b * p.k_bs + (int64_t)hkv * p.k_hs + c * 8;
-  const bf16* Vb = (const bf16*)p.v + (int64_t)b * p.v_bs + (int64_t)hkv * p.v_hs + c * 8;
-  int j = k0 + wave * kWaveKeys + grp;
-  u32x4 kraw{}, vraw{};
-  if (j < k1) {
-    kraw = *reinterpret_cast<const u32x4*>(Kb + (int64_t)j * p.k_ss);
-    vraw = *reinterpret_cast<const u32x4*>(Vb + (int64_t)j * p.v_ss);
-  }
-  float q[R][8];
-  int rlen[TT];  // keys token t0 + tt sees; 0 for a token past T (last tile of an uneven tiling)
-#pragma unroll
-  for (int tt = 0; tt < TT; ++tt) rlen[tt] = t0 + tt < p.T ? len - (p.T - 1 - (t0 + tt)) : 0;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int t = min(t0 + r / G, p.T - 1);  // a token past T reads token T - 1's q and uses none of it
-    const bf16* qp = (const bf16*)p.q + (int64_t)b * p.q_bs + (int64_t)t * p.q_ts +
-                     (int64_t)(hkv * G + r % G) * p.q_hs + c * 8;
-    bf16x8_to_f32(*reinterpret_cast<const u32x4*>(qp), q[r]);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) q[r][i] *= p.scale_log2;
-  }
-  float m[R], l[R], o[R][8];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    m[r] = -INFINITY;
-    l[r] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[r][i] = 0.f;
-  }
-  for (; j < k1; j += kStep) {
-    float kf[8], vf[8];
-    bf16x8_to_f32(kraw, kf);
-    bf16x8_to_f32(vraw, vf);
-    if (j + kStep < k1) {
-      kraw = *reinterpret_cast<const u32x4*>(Kb + (int64_t)(j + kStep) * p.k_ss);
-      vraw = *reinterpret_cast<const u32x4*>(Vb + (int64_t)(j + kStep) * p.v_ss);
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s = fmaf(q[r][i], kf[i], s);
-#pragma unroll
-      for (int off = kLanes / 2; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-      if (j < rlen[r / G]) {  // uniform over the lanes of a key; the shuffles above stay outside
-        const float mn = fmaxf(m[r], s);
-        const float a = fast_exp2(m[r] - mn), e = fast_exp2(s - mn);
-        l[r] = l[r] * a + e;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[r][i] = fmaf(o[r][i], a, e * vf[i]);
-        m[r] = mn;
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-#pragma unroll
-    for (int off = kLanes; off <= 32; off <<= 1) {
-      const float m2 = __shfl_xor(m[r], off, 64), l2 = __shfl_xor(l[r], off, 64);
-      const float mn = fmaxf(m[r], m2);
-      const float a = mn == -INFINITY ? 0.f : fast_exp2(m[r] - mn);
-      const float a2 = mn == -INFINITY ? 0.f : fast_exp2(m2 - mn);
-      l[r] = l[r] * a + l2 * a2;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[r][i] = o[r][i] * a + __shfl_xor(o[r][i], off, 64) * a2;
-      m[r] = mn;
-    }
-    if (grp == 0) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) sm_o[wave][r][c * 8 + i] = o[r][i];
-      if (c == 0) { sm_m[wave][r] = m[r]; sm_l[wave][r] = l[r]; }
-    }
-  }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < R * D; idx += 256) {
-    const int r = idx / D, d = idx % D;
-    const int t = t0 + r / G, hq = hkv * G + r % G;
-    if (t >= p.T) continue;
-    float mm = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) mm = fmaxf(mm, sm_m[w][r]);
-    float ll = 0.f, oo = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float a = mm == -INFINITY ? 0.f : fast_exp2(sm_m[w][r] - mm);
-      ll += sm_l[w][r] * a;
-      oo += sm_o[w][r][d] * a;
-    }
-    if constexpr (D == 64) {
-      if (p.NS == 1) {  // short cache, one split: this is the whole softmax, no combine launch
-        bf16* op = (bf16*)p.o + (int64_t)b * p.o_bs + (int64_t)t * p.o_ts + (int64_t)hq * p.o_hs + d;
-        *op = static_cast<bf16>(ll > 0.f ? oo / ll : 0.f);
-        continue;
-      }
-    }
-    const int64_t slot = (((int64_t)(b * p.T + t) * p.Hq + hq) * p.NS + split);
-    p.part_o[slot * D + d] = oo;
-    if (d == 0) { p.part_m[slot] = mm; p.part_l[slot] = ll; }
-  }
-}
-
-template <int D, int G, int TT>
-void launch_multi_split(const AttnDecodeParams& p, hipStream_t s) {
+void launch_split(const AttnDecodeParams& p, hipStream_t s) {
   const dim3 grid((unsigned)(p.B * p.Hkv), (unsigned)p.NS, (unsigned)((p.T + TT - 1) / TT));
-  hipLaunchKernelGGL((attn_decode_multi_split_kernel<D, G, TT>), grid, dim3(256), 0, s, p);
+  hipLaunchKernelGGL((attn_decode_split_kernel<D, G, TT>), grid, dim3(256), 0, s, p);
 }
 
 template <int D, int G>
-void launch_multi_tokens(const AttnDecodeParams& p, hipStream_t s) {
+void launch_tokens(const AttnDecodeParams& p, hipStream_t s) {
+  if (p.T == 1) return launch_split<D, G, 1>(p, s);
   if constexpr (G == 8) {
-    launch_multi_split<D, 8, 2>(p, s);  // T = 3, 4: two token tiles (see above)
+    launch_split<D, 8, 2>(p, s);  // T = 3, 4: two token tiles (see above)
   } else {
-    if (p.T == 2) launch_multi_split<D, G, 2>(p, s);
-    else if (p.T == 3) launch_multi_split<D, G, 3>(p, s);
-    else launch_multi_split<D, G, 4>(p, s);
+    if (p.T == 2) launch_split<D, G, 2>(p, s);
+    else if (p.T == 3) launch_split<D, G, 3>(p, s);
+    else launch_split<D, G, 4>(p, s);
   }
 }
 
 template <int D>
-void launch_decode_multi(const AttnDecodeParams& p, hipStream_t s) {
+void launch_decode(const AttnDecodeParams& p, hipStream_t s) {
   switch (p.Hq / p.Hkv) {
-    case 1: launch_multi_tokens<D, 1>(p, s); break;
-    case 2: launch_multi_tokens<D, 2>(p, s); break;
-    case 4: launch_multi_tokens<D, 4>(p, s); break;
-    default: launch_multi_tokens<D, 8>(p, s); break;
+    case 1: launch_tokens<D, 1>(p, s); break;
+    case 2: launch_tokens<D, 2>(p, s); break;
+    case 4: launch_tokens<D, 4>(p, s); break;
+    default: launch_tokens<D, 8>(p, s); break;
   }
-  if (D == 64 && p.NS == 1) return;
-  // the combine kernel sees [B * T] sequences of one token: (b, t) is its batch index
+  if (D == 64 && p.NS == 1) return;  // the split kernel wrote the output itself
+  // the combine kernel sees [B * T] sequences of one token: (b, t) is its batch index (with T = 1
+  // the two strides of a contiguous o are the same number)
   AttnDecodeParams c = p;
   c.o_bs = p.o_ts;
   hipLaunchKernelGGL(attn_decode_combine_kernel<D>, dim3((unsigned)(p.B * p.T * p.Hq)), dim3(D), 0, s, c);
@@ -371,12 +256,9 @@ int attn_decode_splits(int B, int Hkv, int Sk, int head_dim) {
   return ns < 1 ? 1 : ns;
 }
 
-void attn_decode(const AttnDecodeParams& p, hipStream_t s) { launch_decode<128>(p, s); }
-
-void attn_decode_d64(const AttnDecodeParams& p, hipStream_t s) { launch_decode<64>(p, s); }
-
-void attn_decode_multi(const AttnDecodeParams& p, hipStream_t s) { launch_decode_multi<128>(p, s); }
-
-void attn_decode_multi_d64(const AttnDecodeParams& p, hipStream_t s) { launch_decode_multi<64>(p, s); }
+void attn_decode(const AttnDecodeParams& p, int head_dim, hipStream_t s) {
+  if (head_dim == 64) launch_decode<64>(p, s);
+  else launch_decode<128>(p, s);
+}
 
 }  // namespace grt

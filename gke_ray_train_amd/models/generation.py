@@ -12,7 +12,7 @@ On MI355X the one-token decode step is launch-bound (≈10 kernels per layer, a 
 each), so ``GraphDecoder`` captures the WHOLE step — embedding, every layer, final norm, LM head
 and, when it is given a ``SamplerConfig``, the choice of the token — into one HIP graph and replays
 it per token. Everything that changes between tokens lives in device tensors the graph reads: the
-current position (RoPE position array and the KV-cache write index) and the per-row valid key
+current position (one per row: RoPE position and KV-cache slot) and the per-row valid key
 length, which the flash kernel takes as its padding mask (``seqlens_k``) over the full-length
 cache, so the kernel's tile loop still covers only the keys written so far.
 
@@ -34,15 +34,12 @@ logits, seed and counter give the same token on either device.
 Prompt-lookup speculative decoding (``generate(..., prompt_lookup_num_tokens=K)``, one sequence)
 replaces the one-token step by a VERIFY step of T = K + 1 tokens: the last emitted token, not yet
 in the cache, and K drafts copied from where the last n-gram occurred before in the prompt and the
-tokens so far. The step is the generic layer step on T rows (``rope_append`` with one position per
-token, the multi-token split-K attention ``attn_decode_multi``, in which token t sees the keys up
-to its own), the LM head on T rows, the sampler's candidate mode (row t draws the token of token
-number n + t) and ``spec_advance`` (csrc/kernels/spec.hip), which keeps the drafts that equal the
-candidates before them, emits 1 .. T tokens, moves positions, valid length and counters on by that
-number and drafts for the next replay — so the loop is still graph replays and one host read per
-``sync_every`` of them. The slots of rejected drafts lie past the valid length and are rewritten by
-the next step; a finished or full row is inert. ``ops/_ref.py::prompt_lookup_draft`` and
-``::spec_accept`` are the host implementations, which the host loops (``device_loop=False``,
+tokens so far. It is the same captured step with T rows (one position per token; split-K decode
+attention in which token t sees the keys up to its own) and another tail: the sampler's candidate
+mode and ``spec_advance`` (see ``GraphDecoder``), so the loop is still graph replays and one host
+read per ``sync_every`` of them. The slots of rejected drafts lie past the valid length and are
+rewritten by the next step; a finished or full row is inert. ``ops/_ref.py::prompt_lookup_draft``
+and ``::spec_accept`` are the host implementations, which the host loops (``device_loop=False``,
 ``use_graph=False``) run on the logits [T, V] of the same step.
 """
 from __future__ import annotations
@@ -109,19 +106,41 @@ def _compact(ids: torch.Tensor, rows: _MaskRows) -> torch.Tensor:
     return torch.where(j < lens, picked, torch.zeros_like(picked))
 
 
-def _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache: KVCache, li: int, row_pos=None):
+def _row_prompt(input_ids: torch.Tensor, rows: Optional[_MaskRows]) -> torch.Tensor:
+    """The masked tokens [n] of a batch of one row."""
+    return input_ids[0] if rows is None else input_ids[0, rows.start[0]:rows.start[0] + rows.lens[0]]
+
+
+def _cache_dtype(model) -> torch.dtype:
+    dt = next(model.parameters()).dtype
+    return dt if dt in (torch.bfloat16, torch.float32) else torch.bfloat16
+
+
+def _layers(model, h, attend):
+    """The layer skeleton of every cached step (norm, qkv, attention, o_proj, norm, MLP) over all
+    layers, then the final norm. ``attend(li, attn, qkv)`` is the RoPE / cache-append / attention
+    middle of layer ``li`` (``_eager_attention`` or ``_device_attention``); it returns
+    o [rows, hq * D]."""
+    residual = None
+    for li, layer in enumerate(model.model.layers):
+        attn = layer.self_attn
+        eps = layer.input_layernorm.eps
+        if residual is None:
+            residual = h
+            x = ops.rms_norm(h, layer.input_layernorm.weight, eps)
+        else:
+            x, residual = ops.add_rms_norm(h, residual, layer.input_layernorm.weight, eps)
+        h = attn.o_proj(attend(li, attn, attn.qkv_proj(x)))
+        x, residual = ops.add_rms_norm(h, residual, layer.post_attention_layernorm.weight, eps)
+        h = _mlp(layer.mlp, x)
+    return ops.add_rms_norm(h, residual, model.model.norm.weight, model.model.norm.eps)[0]
+
+
+def _eager_attention(attn, qkv, B, S, pos0, cos, sin, cache: KVCache, li: int, row_pos=None):
     """``row_pos`` [B] int32: the one-token step of a ragged cache, row b's token at position and
     cache slot row_pos[b]; without it the S tokens of every row sit at pos0 ... pos0 + S - 1."""
-    attn = layer.self_attn
-    eps = layer.input_layernorm.eps
-    if residual is None:
-        residual = h
-        x = ops.rms_norm(h, layer.input_layernorm.weight, eps)
-    else:
-        x, residual = ops.add_rms_norm(h, residual, layer.input_layernorm.weight, eps)
-    qkv = attn.qkv_proj(x)
     hq, hkv, D = attn.hq, attn.hkv, attn.hd
-    pos = row_pos if row_pos is not None else torch.arange(pos0, pos0 + S, device=h.device, dtype=torch.int32).repeat(B)
+    pos = row_pos if row_pos is not None else torch.arange(pos0, pos0 + S, device=qkv.device, dtype=torch.int32).repeat(B)
     if _fused_ok(qkv, cache, li):
         # RoPE of q / k and the cache append of k / v in one kernel (rope_append, elementwise.hip)
         q = _native.kernels().rope_append(qkv.contiguous(), cos, sin, pos, hq, hkv, D, cos.shape[0],
@@ -135,7 +154,7 @@ def _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache: KVCache, li: in
             cache.k[li][:, pos0:pos0 + S] = k.view(B, S, hkv, D)
             cache.v[li][:, pos0:pos0 + S] = v
         else:
-            b = torch.arange(B, device=h.device)
+            b = torch.arange(B, device=qkv.device)
             cache.k[li][b, row_pos.long()] = k.view(B, hkv, D)
             cache.v[li][b, row_pos.long()] = v[:, 0]
     kk = cache.k[li][:, :pos0 + S]
@@ -144,9 +163,21 @@ def _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache: KVCache, li: in
         o = ops.flash_attention(q.view(B, S, hq, D), kk, vv, causal=True)
     else:  # slots past a short row's own tokens hold the prefill's filler: masked by the valid length
         o = ops.flash_attention(q.view(B, 1, hq, D), kk, vv, causal=False, seqlens_k=row_pos + 1)
-    h = attn.o_proj(o.reshape(B * S, hq * D))
-    x, residual = ops.add_rms_norm(h, residual, layer.post_attention_layernorm.weight, eps)
-    return _mlp(layer.mlp, x), residual
+    return o.reshape(B * S, hq * D)
+
+
+def _device_attention(attn, qkv, B, T, cos, sin, cache: KVCache, li: int, pos_b, lens):
+    """The captured step's middle, every position read from device tensors: T tokens per row at
+    positions and cache slots pos_b [B * T] (rows differ after a masked prefill), the last T of the
+    row's ``lens`` valid keys. ``T`` > 1 is the verify step of speculative decoding."""
+    hq, hkv, D = attn.hq, attn.hkv, attn.hd
+    q = _native.kernels().rope_append(qkv.contiguous(), cos, sin, pos_b, hq, hkv, D, cos.shape[0],
+                                      cache.k[li], cache.v[li], T)
+    if T == 1:
+        o = ops.flash_attention(q.view(B, 1, hq, D), cache.k[li], cache.v[li], causal=False, seqlens_k=lens)
+    else:
+        o = ops.decode_attention_multi(q.view(B, T, hq, D), cache.k[li], cache.v[li], seqlens_k=lens)
+    return o.reshape(B * T, hq * D)
 
 
 def _fused_ok(qkv, cache: KVCache, li: int) -> bool:
@@ -201,10 +232,7 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache, attention_mask=None
         raise ValueError(f"KV cache overflow: {pos0} cached + {S} new tokens > max_len {cache.max_len}")
     cos, sin = model.rope(cache.max_len, ids.device)
     h = model.model.embed_tokens(ids).view(B * S, -1)
-    residual = None
-    for li, layer in enumerate(model.model.layers):
-        h, residual = _layer_step(layer, h, residual, B, S, pos0, cos, sin, cache, li, row_pos)
-    x, _ = ops.add_rms_norm(h, residual, model.model.norm.weight, model.model.norm.eps)
+    x = _layers(model, h, lambda li, attn, qkv: _eager_attention(attn, qkv, B, S, pos0, cos, sin, cache, li, row_pos))
     if all_logits:
         if rows is not None or row_pos is not None:
             raise ValueError("forward_cached: all_logits needs an unpadded, non-ragged cache")
@@ -219,31 +247,6 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache, attention_mask=None
             cache.lens = row_pos + 1
     cache.len += S
     return model.lm_head(last).float()
-
-
-def _graph_layer_step(layer, h, residual, B, cos, sin, cache: KVCache, li: int, pos_b, pos_l, lens, T: int = 1):
-    """One-token layer step with every position-dependent value read from device tensors. ``T`` >
-    1 is the verify step of speculative decoding: T tokens per row at positions pos_b [B * T], the
-    last T of the row's ``lens`` valid keys, through the multi-token decode attention."""
-    attn = layer.self_attn
-    eps = layer.input_layernorm.eps
-    if residual is None:
-        residual = h
-        x = ops.rms_norm(h, layer.input_layernorm.weight, eps)
-    else:
-        x, residual = ops.add_rms_norm(h, residual, layer.input_layernorm.weight, eps)
-    qkv = attn.qkv_proj(x)
-    hq, hkv, D = attn.hq, attn.hkv, attn.hd
-    # the new token's position is its cache slot, one per row (rows differ after a masked prefill)
-    q = _native.kernels().rope_append(qkv.contiguous(), cos, sin, pos_b, hq, hkv, D, cos.shape[0],
-                                      cache.k[li], cache.v[li], T)
-    if T == 1:
-        o = ops.flash_attention(q.view(B, 1, hq, D), cache.k[li], cache.v[li], causal=False, seqlens_k=lens)
-    else:
-        o = ops.decode_attention_multi(q.view(B, T, hq, D), cache.k[li], cache.v[li], seqlens_k=lens)
-    h = attn.o_proj(o.reshape(B * T, hq * D))
-    x, residual = ops.add_rms_norm(h, residual, layer.post_attention_layernorm.weight, eps)
-    return _mlp(layer.mlp, x), residual
 
 
 _GEMV_NORM = os.environ.get("GRT_GEMV_NORM", "1") != "0"
@@ -378,28 +381,24 @@ class GraphDecoder:
             self.T = spec.num_tokens + 1
         T = self.T
         self.n_replays = 0
-        p = next(model.parameters())
-        self.device = p.device
-        dt = p.dtype if p.dtype in (torch.bfloat16, torch.float32) else torch.bfloat16
-        self.cache = KVCache(model.config, B, max_len, self.device, dt)
+        self.device = dev = next(model.parameters()).device
+        self.cache = KVCache(model.config, B, max_len, dev, _cache_dtype(model))
         self.B = B
-        self.cos, self.sin = model.rope(max_len, self.device)
-        self.ids = torch.zeros(B, T, dtype=torch.long, device=self.device)
-        self.pos_b = torch.zeros(B * T, dtype=torch.int32, device=self.device)   # RoPE positions
-        self.pos_l = torch.zeros(1, dtype=torch.long, device=self.device)    # cache write index
-        self.lens = torch.zeros(B, dtype=torch.int32, device=self.device)    # valid keys incl. new token
+        self.cos, self.sin = model.rope(max_len, dev)
+        self.ids = torch.zeros(B, T, dtype=torch.long, device=dev)
+        self.pos_b = torch.zeros(B * T, dtype=torch.int32, device=dev)   # RoPE positions = cache slots
+        self.lens = torch.zeros(B, dtype=torch.int32, device=dev)        # valid keys incl. new token
         self.graph = None
         self.logits = None
         # residual adds / norms inside the GEMVs when every projection is a plain bf16 Linear
-        self.norm_ws = (_NormWorkspace(B, self.device)
-                        if self.device.type == "cuda" and spec is None and _norm_fusable(model, B) else None)
+        self.norm_ws = (_NormWorkspace(B, dev)
+                        if dev.type == "cuda" and spec is None and _norm_fusable(model, B) else None)
         self.sampler = sampler
         if sampler is not None:
             if len(sampler.eos_ids) > SAMPLER_MAX_EOS:
                 raise ValueError(f"the device sampler takes at most {SAMPLER_MAX_EOS} EOS ids, got {len(sampler.eos_ids)}")
             if sampler.max_new_tokens < 1:
                 raise ValueError("SamplerConfig.max_new_tokens must be >= 1")
-            dev = self.device
             self.finished = torch.zeros(B, dtype=torch.bool, device=dev)
             self.finish_step = torch.full((B,), -1, dtype=torch.long, device=dev)
             self.n_step = torch.zeros(1, dtype=torch.long, device=dev)    # column of `out` the next token takes
@@ -408,7 +407,6 @@ class GraphDecoder:
             self.eos_t = (torch.tensor(sorted(sampler.eos_ids), dtype=torch.long, device=dev)
                           if sampler.eos_ids else None)
         if spec is not None:
-            dev = self.device
             self._ar = torch.arange(T, dtype=torch.int32, device=dev)
             self.cand = torch.zeros(T, dtype=torch.long, device=dev)              # the sampler's candidates
             self.drafts = torch.full((T - 1,), -1, dtype=torch.long, device=dev)  # as drawn (-1: none)
@@ -468,7 +466,6 @@ class GraphDecoder:
             return self._spec_prefill(input_ids, attention_mask)
         logits = forward_cached(self.model, input_ids, self.cache, attention_mask)
         n = self.cache.len
-        self.pos_l.fill_(n)
         if self.cache.lens is None:
             self.pos_b.fill_(n)
             self.lens.fill_(n + 1)
@@ -483,7 +480,7 @@ class GraphDecoder:
         from then on nothing differs). The positions are left one short of the first verify step's:
         ``first_token`` emits exactly one token and ``spec_advance`` moves them on by it."""
         rows = _mask_rows(attention_mask, 1, input_ids.shape[1])
-        prompt = input_ids[0] if rows is None else input_ids[0, rows.start[0]:rows.start[0] + rows.lens[0]]
+        prompt = _row_prompt(input_ids, rows)
         logits = forward_cached(self.model, input_ids, self.cache, rows)
         n = prompt.shape[0]
         self.cache.len, self.cache.lens = n, None
@@ -497,53 +494,41 @@ class GraphDecoder:
 
     @torch.no_grad()
     def _step_body(self):
-        m = self.model
-        if self.spec is not None:
-            T = self.T
-            h = m.model.embed_tokens(self.ids).view(T, -1)
-            residual = None
-            for li, layer in enumerate(m.model.layers):
-                h, residual = _graph_layer_step(layer, h, residual, 1, self.cos, self.sin, self.cache, li,
-                                                self.pos_b, self.pos_l, self.lens, T=T)
-            x, _ = ops.add_rms_norm(h, residual, m.model.norm.weight, m.model.norm.eps)
-            logits = m.lm_head(x)  # [T, V]
-            if self.sampler is None:
-                return logits.float()
-            self._spec_sample(logits)  # moves the positions on by the number of tokens emitted
-            return logits
-        h = m.model.embed_tokens(self.ids).view(self.B, -1)
+        """Embedding, layers, logits [B * T, V], tail."""
+        m, B, T = self.model, self.B, self.T
+        h = m.model.embed_tokens(self.ids).view(B * T, -1)
         if self.norm_ws is not None:
             for li, layer in enumerate(m.model.layers):
-                h = _fused_norm_layer_step(layer, h, li == 0, self.norm_ws, self.B, self.cos, self.sin,
+                h = _fused_norm_layer_step(layer, h, li == 0, self.norm_ws, B, self.cos, self.sin,
                                            self.cache, li, self.pos_b, self.lens)
             fn = m.model.norm
             logits = _native.kernels().gemv_fused(h, m.lm_head.weight, self.norm_ws.sumsq, 1, g=fn.weight,
                                                   eps=fn.eps)
-            return self._step_tail(logits)
-        residual = None
-        for li, layer in enumerate(m.model.layers):
-            h, residual = _graph_layer_step(layer, h, residual, self.B, self.cos, self.sin, self.cache, li,
-                                            self.pos_b, self.pos_l, self.lens)
-        x, _ = ops.add_rms_norm(h, residual, m.model.norm.weight, m.model.norm.eps)
-        return self._step_tail(m.lm_head(x))
+        else:
+            logits = m.lm_head(_layers(m, h, lambda li, attn, qkv: _device_attention(
+                attn, qkv, B, T, self.cos, self.sin, self.cache, li, self.pos_b, self.lens)))
+        return self._step_tail(logits)
 
     def _step_tail(self, logits):
         """End of the step: the sampler reads the LM head's bf16 logits as they are; without one
-        the caller gets an fp32 copy. Then the positions move on."""
-        if self.sampler is not None:
-            self._sample(logits)
-        else:
+        the caller gets an fp32 copy. Then the positions move on by one token; those of a verify
+        step are moved by ``spec_advance``, by the number of tokens emitted, or set by ``step_spec``."""
+        if self.sampler is None:
             logits = logits.float()
-        self.pos_b.add_(1)
-        self.pos_l.add_(1)
-        self.lens.add_(1)
+        elif self.spec is not None:
+            self._spec_sample(logits)
+        else:
+            self._sample(logits)
+        if self.spec is None:
+            self.pos_b.add_(1)
+            self.lens.add_(1)
         return logits
 
     def _capture(self):
         # warm up on a side stream (allocator pools, library handles), then capture one step;
         # the warm-up step's cache writes land at the current position and are rewritten by the
         # first replay, and the position tensors are restored afterwards
-        state = [self.pos_b, self.pos_l, self.lens]
+        state = [self.pos_b, self.lens]
         if self.sampler is not None:  # the sampler's epilogue writes these; column n_step of `out`
             # is written again, with the same token, by the first replay
             state += [self.ids, self.finished, self.finish_step, self.n_step, self.counter]
@@ -573,17 +558,18 @@ class GraphDecoder:
             # the positions live on the device and a finished or full row is inert: a replay past the
             # end writes cache slots below prompt + max_new_tokens + K only (generate() sizes the
             # cache so), and rope_append skips any position outside the cache
-            if self.graph is None:
-                self._capture()
-            self.graph.replay()
-            self.n_replays += 1
-            return
+            return self._replay()
         if self.cache.len >= self.cache.max_len:
             raise RuntimeError("KV cache full")
+        self._replay()
+        self.cache.len += 1
+
+    def _replay(self) -> None:
+        """One replay of the captured step, captured at the first one."""
         if self.graph is None:
             self._capture()
         self.graph.replay()
-        self.cache.len += 1
+        self.n_replays += 1
 
     @torch.no_grad()
     def step_spec(self, ids: torch.Tensor, p: int) -> torch.Tensor:
@@ -596,10 +582,7 @@ class GraphDecoder:
         self.ids.copy_(ids.view(1, self.T))
         self.pos_b.copy_(self._ar + p)
         self.lens.fill_(p + self.T)
-        if self.graph is None:
-            self._capture()
-        self.graph.replay()
-        self.n_replays += 1
+        self._replay()
         return self.logits
 
     @torch.no_grad()
@@ -611,9 +594,7 @@ class GraphDecoder:
         if self.cache.len >= self.cache.max_len:
             raise RuntimeError("KV cache full")
         self.ids.copy_(next_ids.view(self.B, 1))
-        if self.graph is None:
-            self._capture()
-        self.graph.replay()
+        self._replay()
         self.cache.len += 1
         return self.logits
 
@@ -653,7 +634,7 @@ def _spec_generate(model, input_ids, rows, P: int, sampler: SamplerConfig, spec:
         n = dec.n_emitted
         last_spec_stats.update(n_replays=dec.n_replays, n_emitted=n)
         return dec.out[0, :n]
-    prompt = input_ids[0] if rows is None else input_ids[0, rows.start[0]:rows.start[0] + rows.lens[0]]
+    prompt = _row_prompt(input_ids, rows)
     if graph:
         dec = GraphDecoder(model, 1, max_len, spec=spec)
         first = dec.prefill(input_ids, rows)
@@ -661,9 +642,7 @@ def _spec_generate(model, input_ids, rows, P: int, sampler: SamplerConfig, spec:
         def step(ids, p):
             return dec.step_spec(torch.tensor(ids, device=dev), p)
     else:
-        pm = next(model.parameters())
-        cache = KVCache(model.config, 1, max_len, dev,
-                        pm.dtype if pm.dtype in (torch.bfloat16, torch.float32) else torch.bfloat16)
+        cache = KVCache(model.config, 1, max_len, dev, _cache_dtype(model))
         first = forward_cached(model, input_ids, cache, rows)
         cache.lens = None  # one row: nothing is ragged once its tokens sit at 0 ... P - 1
 
@@ -753,118 +732,131 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     ``last_spec_stats`` holds the verify steps and tokens of the latest such call."""
     was = model.training
     model.eval()
-    B, S = input_ids.shape
-    rows = _mask_rows(attention_mask, B, S)
-    P = S if rows is None else max(rows.lens)  # the longest prompt: the cache holds P + max_new_tokens
-    eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
-    eos_t = torch.tensor(sorted(eos), device=input_ids.device) if eos else None
-    graph = use_graph if use_graph is not None else _graph_ok(model, input_ids)
-    temperature = max(temperature, 1e-5)
-    top_k = int(top_k) if top_k else 0
-    top_p = 1.0 if top_p is None else float(top_p)
-    if top_k < 0 or not 0.0 < top_p <= 1.0:
-        raise ValueError(f"generate: top_k must be >= 0 and top_p in (0, 1], got top_k={top_k}, top_p={top_p}")
-    if do_sample and generator is None and seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # torch's default generator: torch.manual_seed governs
-    seed = int(seed or 0)
-    can = _device_loop_ok(graph, generator, len(eos), max_new_tokens)
-    if device_loop and not can:
-        raise ValueError("generate: device_loop=True needs the graph path (bf16 model on the GPU, native kernels), "
-                         f"no generator, at most {SAMPLER_MAX_EOS} EOS ids and max_new_tokens >= 1")
-    K = int(prompt_lookup_num_tokens or 0)
-    if K:
-        N = int(max_matching_ngram_size)
-        limit = model.config.max_position_embeddings
-        if not 1 <= K <= SPEC_MAX_DRAFTS:
-            raise ValueError(f"generate: prompt_lookup_num_tokens must be in 1..{SPEC_MAX_DRAFTS} (the verify step runs "
-                             f"K + 1 <= {SPEC_MAX_DRAFTS + 1} rows, the limit of the GEMV kernels), got {K}")
-        if N < 1:
-            raise ValueError(f"generate: max_matching_ngram_size must be >= 1, got {N}")
-        if B != 1:
-            raise ValueError(f"generate: prompt lookup decoding takes a batch of 1, got {B} sequences")
-        if generator is not None:
-            raise ValueError("generate: prompt lookup decoding needs the counter-based noise (seed=...), not a "
-                             "torch generator: a draft is accepted iff it is the token drawn at its token number")
-        if P + max_new_tokens + K > limit:
-            raise ValueError(f"generate: prompt ({P}) + max_new_tokens ({max_new_tokens}) + prompt_lookup_num_tokens "
-                             f"({K}) exceeds max_position_embeddings ({limit}), the extent of the RoPE table")
-    if K and max_new_tokens >= 1:
+    try:
+        B, S = input_ids.shape
+        rows = _mask_rows(attention_mask, B, S)
+        P = S if rows is None else max(rows.lens)  # the longest prompt: the cache holds P + max_new_tokens
+        eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
+        graph = use_graph if use_graph is not None else _graph_ok(model, input_ids)
+        temperature = max(temperature, 1e-5)
+        top_k = int(top_k) if top_k else 0
+        top_p = 1.0 if top_p is None else float(top_p)
+        if top_k < 0 or not 0.0 < top_p <= 1.0:
+            raise ValueError(f"generate: top_k must be >= 0 and top_p in (0, 1], got top_k={top_k}, top_p={top_p}")
+        if do_sample and generator is None and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # torch's default generator: torch.manual_seed governs
+        seed = int(seed or 0)
+        can = _device_loop_ok(graph, generator, len(eos), max_new_tokens)
+        if device_loop and not can:
+            raise ValueError("generate: device_loop=True needs the graph path (bf16 model on the GPU, native kernels), "
+                             f"no generator, at most {SAMPLER_MAX_EOS} EOS ids and max_new_tokens >= 1")
+        K = int(prompt_lookup_num_tokens or 0)
+        if K:
+            N = int(max_matching_ngram_size)
+            limit = model.config.max_position_embeddings
+            if not 1 <= K <= SPEC_MAX_DRAFTS:
+                raise ValueError(f"generate: prompt_lookup_num_tokens must be in 1..{SPEC_MAX_DRAFTS} (the verify step "
+                                 f"runs K + 1 <= {SPEC_MAX_DRAFTS + 1} rows, the limit of the GEMV kernels), got {K}")
+            if N < 1:
+                raise ValueError(f"generate: max_matching_ngram_size must be >= 1, got {N}")
+            if B != 1:
+                raise ValueError(f"generate: prompt lookup decoding takes a batch of 1, got {B} sequences")
+            if generator is not None:
+                raise ValueError("generate: prompt lookup decoding needs the counter-based noise (seed=...), not a "
+                                 "torch generator: a draft is accepted iff it is the token drawn at its token number")
+            if P + max_new_tokens + K > limit:
+                raise ValueError(f"generate: prompt ({P}) + max_new_tokens ({max_new_tokens}) + "
+                                 f"prompt_lookup_num_tokens ({K}) exceeds max_position_embeddings ({limit}), the "
+                                 "extent of the RoPE table")
         sampler = SamplerConfig(max_new_tokens=max_new_tokens, do_sample=do_sample, temperature=temperature, top_k=top_k,
                                 top_p=top_p, seed=seed, eos_ids=tuple(sorted(eos)), pad_id=pad_token_id)
-        spec = SpecConfig(K, N, _spec_plan)
         on_device = can and (device_loop if device_loop is not None else _DEVICE_SAMPLER)
-        new = _spec_generate(model, input_ids, rows, P, sampler, spec, graph, on_device, sync_every)
+        if K and max_new_tokens >= 1:
+            new = _spec_generate(model, input_ids, rows, P, sampler, SpecConfig(K, N, _spec_plan), graph, on_device,
+                                 sync_every)[None]
+        elif on_device:
+            new = _device_loop(model, input_ids, rows, P, sampler, sync_every)
+        else:
+            new = _host_loop(model, input_ids, rows, P, sampler, graph, generator, sync_every)
+        return torch.cat([input_ids, new], 1)
+    finally:
         if was:
             model.train()
-        return torch.cat([input_ids, new[None]], 1)
-    if can and (device_loop if device_loop is not None else _DEVICE_SAMPLER):
-        cfg = SamplerConfig(max_new_tokens=max_new_tokens, do_sample=do_sample, temperature=temperature, top_k=top_k,
-                            top_p=top_p, seed=seed, eos_ids=tuple(sorted(eos)), pad_id=pad_token_id)
-        dec = GraphDecoder(model, B, P + max_new_tokens, sampler=cfg)
-        dec.first_token(dec.prefill(input_ids, rows))
-        done = 1
-        while done < max_new_tokens:
-            # replays up to the next multiple of sync_every tokens, then one host read
-            for _i in range(min(sync_every - done % sync_every, max_new_tokens - done)):
-                dec.advance()
-                done += 1
-            if eos and done % sync_every == 0 and bool(dec.finished.all()):
-                break
-        if eos:  # HF stops right after the token that finished the last row
-            last = dec.finish_step.tolist()
-            if min(last) >= 0:
-                done = max(last) + 1
-        if was:
-            model.train()
-        return torch.cat([input_ids, dec.out[:, :done]], 1)
+
+
+def _device_loop(model, input_ids, rows, P: int, sampler: SamplerConfig, sync_every: int) -> torch.Tensor:
+    """The new tokens [B, n] with the token picked inside the captured step."""
+    new, eos = sampler.max_new_tokens, sampler.eos_ids
+    dec = GraphDecoder(model, input_ids.shape[0], P + new, sampler=sampler)
+    dec.first_token(dec.prefill(input_ids, rows))
+    done = 1
+    while done < new:
+        # replays up to the next multiple of sync_every tokens, then one host read
+        for _i in range(min(sync_every - done % sync_every, new - done)):
+            dec.advance()
+            done += 1
+        if eos and done % sync_every == 0 and bool(dec.finished.all()):
+            break
+    if eos:  # HF stops right after the token that finished the last row
+        last = dec.finish_step.tolist()
+        if min(last) >= 0:
+            done = max(last) + 1
+    return dec.out[:, :done]
+
+
+def _multinomial_pick(logits, temperature: float, top_k: int, top_p: float, generator) -> torch.Tensor:
+    """A ``torch.multinomial`` draw per row after temperature, top-k and top-p, as HF chains them."""
+    probs = torch.softmax(logits / temperature, -1)
+    if 0 < top_k < probs.shape[-1]:
+        kth = probs.topk(top_k, -1).values[..., -1:]
+        probs = torch.where(probs < kth, torch.zeros_like(probs), probs)
+        probs = probs / probs.sum(-1, keepdim=True)
+    if top_p < 1.0:
+        sp, si = probs.sort(-1, descending=True)
+        keep = sp.cumsum(-1) - sp <= top_p
+        sp = sp * keep
+        probs = torch.zeros_like(probs).scatter(-1, si, sp)
+    return torch.multinomial(probs / probs.sum(-1, keepdim=True), 1, generator=generator).squeeze(-1)
+
+
+def _host_loop(model, input_ids, rows, P: int, c: SamplerConfig, graph: bool, generator, sync_every: int):
+    """The new tokens [B, n], picked on the host from the logits of the graph's or the eager step."""
+    B, new = input_ids.shape[0], c.max_new_tokens
     if graph:
-        dec = GraphDecoder(model, B, P + max_new_tokens)
+        dec = GraphDecoder(model, B, P + new)
         logits = dec.prefill(input_ids, rows)
         forward = dec.step
     else:
-        p = next(model.parameters())
-        cache = KVCache(model.config, B, P + max_new_tokens, input_ids.device,
-                        p.dtype if p.dtype in (torch.bfloat16, torch.float32) else torch.bfloat16)
+        cache = KVCache(model.config, B, P + new, input_ids.device, _cache_dtype(model))
         logits = forward_cached(model, input_ids, cache, rows)
 
         def forward(nxt):
             return forward_cached(model, nxt[:, None], cache)
-    out = [input_ids]
+    eos_t = torch.tensor(list(c.eos_ids), device=input_ids.device) if c.eos_ids else None
+    out = []
     finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
     all_done = []  # device flags: every row finished after token t
-    for t in range(max_new_tokens):
-        if do_sample and generator is None:
+    for t in range(new):
+        if c.do_sample and generator is None:
             # the device sampler's host implementation: token t draws the noise of counter t
-            nxt = _ref.sample_tokens(logits, seed=seed, counter=t, temperature=temperature, top_k=top_k, top_p=top_p)
-        elif do_sample:
-            probs = torch.softmax(logits / temperature, -1)
-            if 0 < top_k < probs.shape[-1]:
-                kth = probs.topk(top_k, -1).values[..., -1:]
-                probs = torch.where(probs < kth, torch.zeros_like(probs), probs)
-                probs = probs / probs.sum(-1, keepdim=True)
-            if top_p < 1.0:
-                sp, si = probs.sort(-1, descending=True)
-                keep = sp.cumsum(-1) - sp <= top_p
-                sp = sp * keep
-                probs = torch.zeros_like(probs).scatter(-1, si, sp)
-            nxt = torch.multinomial(probs / probs.sum(-1, keepdim=True), 1, generator=generator).squeeze(-1)
+            nxt = _ref.sample_tokens(logits, seed=c.seed, counter=t, temperature=c.temperature, top_k=c.top_k,
+                                     top_p=c.top_p)
+        elif c.do_sample:
+            nxt = _multinomial_pick(logits, c.temperature, c.top_k, c.top_p, generator)
         else:
             nxt = logits.argmax(-1)
-        if pad_token_id is not None:
-            nxt = torch.where(finished, torch.full_like(nxt, pad_token_id), nxt)
+        if c.pad_id is not None:
+            nxt = torch.where(finished, torch.full_like(nxt, c.pad_id), nxt)
         out.append(nxt[:, None])
         if eos_t is not None:
             finished |= torch.isin(nxt, eos_t)
             all_done.append(finished.all())
             if (t + 1) % sync_every == 0 and bool(finished.all()):
                 break
-        if t + 1 < max_new_tokens:
+        if t + 1 < new:
             logits = forward(nxt)
     if all_done:  # HF stops right after the token that finished the last row
         flags = torch.stack(all_done)
         if bool(flags.any()):
-            first = int(flags.nonzero()[0, 0])
-            out = out[:first + 2]
-    if was:
-        model.train()
-    return torch.cat(out, 1)
+            out = out[:int(flags.nonzero()[0, 0]) + 1]
+    return torch.cat([input_ids[:, :0], *out], 1)  # [B, 0] when there is no new token
