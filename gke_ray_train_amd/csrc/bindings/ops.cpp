@@ -975,7 +975,7 @@ std::vector<Tensor> attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& 
   return {dq, dk, dv};
 }
 
-// ---- RoPE + attention on the fused QKV buffer, bf16 head_dim 64 (rope_attention_d64.hip) ----
+// ---- RoPE + attention on the fused QKV buffer, bf16 head_dim 64 (attention_d64.hip, FusedRope policy) ----
 // row stride of t seen as T token rows of Hq heads: [T, Hq * 64] or [T, Hq, 64] with unit last stride and
 // heads 64 apart; the rows may be the head of a wider row buffer
 int64_t d64_row_stride(const Tensor& t, int64_t T, int64_t hq, const char* op, const char* name) {

@@ -268,7 +268,7 @@ void attn_bwd_f32(const AttnBwdParams& p, hipStream_t s);
 bool attn_bf16_supported(int head_dim);
 void attn_fwd_d64(const AttnParams& p, hipStream_t s);
 void attn_bwd_d64(const AttnBwdParams& p, hipStream_t s);
-// bf16 head_dim 64 on the fused QKV buffer (rope_attention_d64.hip): RoPE (rotate-half, position =
+// bf16 head_dim 64 on the fused QKV buffer (attention_d64.hip, FusedRope policy): RoPE (rotate-half, position =
 // row index inside its own sequence) is applied in fp32 where a Q / K row or tile is loaded, and
 // undone on the fp32 dQ / dK accumulators before they are stored, so no rotated copy of q / k and
 // no separate dq / dk exist. Sequence b is token rows [cu[b], cu[b+1]) when cu_seqlens is given

@@ -427,7 +427,7 @@ class _RopeAttention(torch.autograd.Function):
 
 
 # bf16 head_dim 64: RoPE inside the attention kernels, straight from / into the fused QKV rows, one
-# launch set for all packed sequences (rope_attention_d64.hip); GRT_ROPE_ATTN_D64=0 -> torch RoPE,
+# launch set for all packed sequences (attention_d64.hip, FusedRope policy); GRT_ROPE_ATTN_D64=0 -> torch RoPE,
 # then the plain flash kernels (sequence by sequence when packed)
 _ROPE_ATTN_D64 = os.environ.get("GRT_ROPE_ATTN_D64", "1") != "0"
 

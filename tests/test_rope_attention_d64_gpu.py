@@ -1,5 +1,5 @@
 """Fused RoPE + packed flash attention at head_dim 64 on the fused QKV buffer
-(csrc/kernels/rope_attention_d64.hip): the raw bindings, ``ops.rope_attention`` and llama-tiny-d64
+(the FusedRope kernels of csrc/kernels/attention_d64.hip): the raw bindings, ``ops.rope_attention`` and llama-tiny-d64
 against the fp32 math path run sequence by sequence (``_ref.apply_rope`` with the positions of
 ``Varlen.pos``, then ``_ref.attention``)."""
 import functools
@@ -217,6 +217,35 @@ def test_packed_runs_are_bitwise_repeatable():
                 assert torch.equal(x[i, :, :n], y[i, :, :n]), "lse: two runs differ"
         else:
             assert torch.equal(x, y), f"{name}: two runs differ"
+
+
+# ------------------------------------------------------------------ 7b. one kernel, two entry points
+@pytest.mark.parametrize("B,S,hq,hkv,causal", [(2, 200, 8, 2, True), (1, 33, 4, 4, True), (2, 96, 4, 2, False)])
+def test_identity_rotation_equals_the_plain_kernels(B, S, hq, hkv, causal):
+    """attention_d64.hip writes each kernel once for both sources, so with cos = 1, sin = 0 the
+    qkv-native entry points must give the values of attn_fwd / attn_bwd on the q, k, v column
+    views of the same buffer: own * 1 -+ partner * 0 rounds back to the bf16 it came from,
+    a0 * 1 + a1 * 0 is a0 in fp32, and all other arithmetic is shared (finite inputs keep
+    partner * 0 from being NaN). torch.equal compares values, so a zero's sign does not count."""
+    C = _C()
+    torch.manual_seed(4)
+    T, W, sc = B * S, (hq + 2 * hkv) * D, D ** -0.5
+    qkv = torch.randn(T, W, device=DEV, dtype=torch.bfloat16)
+    do = torch.randn(T, hq * D, device=DEV, dtype=torch.bfloat16)
+    cos = torch.ones(S, D // 2, device=DEV)
+    sin = torch.zeros(S, D // 2, device=DEV)
+    buf, lse, dqkv = _raw(qkv, do, cos, sin, hq, hkv, B, S, causal=causal)
+    x = qkv.view(B, S, hq + 2 * hkv, D)
+    q, k, v = x[:, :, :hq], x[:, :, hq:hq + hkv], x[:, :, hq + hkv:]
+    o, lse_p = C.attn_fwd(q, k, v, None, sc, causal, None)
+    dq, dk, dv = C.attn_bwd(do.view(B, S, hq, D), q, k, v, o, lse_p, None, None, None, sc, causal, None)
+    torch.cuda.synchronize()
+    g = dqkv.view(B, S, hq + 2 * hkv, D)
+    assert torch.equal(buf.view(B, S, hq, D), o), "o"
+    assert torch.equal(lse, lse_p), "lse"
+    assert torch.equal(g[:, :, :hq], dq), "dq"
+    assert torch.equal(g[:, :, hq:hq + hkv], dk), "dk"
+    assert torch.equal(g[:, :, hq + hkv:], dv), "dv"
 
 
 # ------------------------------------------------------------------ 8. no fallback, model level

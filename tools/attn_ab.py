@@ -14,7 +14,7 @@ rounds after a warm-up, device events; median, min and max per variant, and for 
 D = 128 kernels at the same B, S, H.
 
 --head-dim 64 --rope [--packed L1,L2,...]: ``ops.rope_attention`` at Hq32 Hkv8 on the qkv-native
-kernels (rope_attention_d64.hip) against the path they replace (GRT_ROPE_ATTN_D64=0 semantics: torch
+kernels (attention_d64.hip, FusedRope policy) against the path they replace (GRT_ROPE_ATTN_D64=0 semantics: torch
 RoPE, then the flash kernels, one call per sequence when packed), unpacked B8 S1024 or the packed
 lengths; same protocol, both arms checked against the fp32 math path first.
 """
@@ -168,7 +168,7 @@ def run_d64(shape, dropout_p, rounds, iters):
 
 
 def run_rope_d64(B, S, lens, rounds, iters, Hq=32, Hkv=8):
-    """``ops.rope_attention`` at head_dim 64, qkv-native kernels (rope_attention_d64.hip) against the
+    """``ops.rope_attention`` at head_dim 64, qkv-native kernels (attention_d64.hip, FusedRope policy) against the
     path they replace (GRT_ROPE_ATTN_D64=0: torch RoPE, then the flash kernels, one call per
     sequence when packed). ``lens``: packed sequence lengths, or None for B sequences of S rows."""
     from gke_ray_train_amd import ops
