@@ -319,6 +319,73 @@ Tensor rope_append(const Tensor& qkv, const Tensor& cos, const Tensor& sin, cons
   return q;
 }
 
+// fp8 KV cache (kv_fp8.hip): codes uint8 [B, L, hkv, D] with unit last stride and 8-byte aligned
+// base and strides, scales fp32 [B, L, hkv] on the same device
+void check_fp8_cache(const Tensor& c, const Tensor& sc, const Tensor& like, const char* op, const char* name) {
+  check_cuda(c, name);
+  check_cuda(sc, name);
+  TORCH_CHECK(c.scalar_type() == at::kByte && c.dim() == 4 && c.stride(3) == 1, op, ": ", name,
+              " must be uint8 codes [B, L, Hkv, D] with unit last stride");
+  TORCH_CHECK(sc.scalar_type() == at::kFloat && sc.dim() == 3 && sc.size(0) == c.size(0) && sc.size(1) == c.size(1) &&
+                  sc.size(2) == c.size(2),
+              op, ": ", name, " scales must be fp32 [B, L, Hkv]");
+  TORCH_CHECK(c.device() == like.device() && sc.device() == like.device(), op, ": ", name, " on the same device");
+  TORCH_CHECK(c.stride(0) % 8 == 0 && c.stride(1) % 8 == 0 && c.stride(2) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(c.data_ptr()) % 8 == 0,
+              op, ": ", name, " needs an 8-byte aligned base pointer and strides");
+}
+
+// rope_append into an fp8 cache: K is rotated, rounded to bf16 and quantised, V quantised; k_out
+// (optional, bf16 [T, hkv, D] contiguous) receives the rotated bf16 K (the prefill attends over it)
+Tensor rope_append_fp8(const Tensor& qkv, const Tensor& cos, const Tensor& sin, const Tensor& pos, int64_t hq,
+                       int64_t hkv, int64_t D, int64_t S, Tensor& kc, Tensor& vc, Tensor& k_scale, Tensor& v_scale,
+                       int64_t tpr, const optional<Tensor>& k_out) {
+  const char* op = "rope_append_fp8";
+  check_cuda(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.stride(1) == 1 && qkv.scalar_type() == at::kBFloat16, "qkv must be bf16 [T, ld]");
+  c10::OptionalDeviceGuard g(qkv.device());
+  const int64_t T = qkv.size(0), ld = qkv.stride(0);
+  TORCH_CHECK(qkv.size(1) >= (hq + 2 * hkv) * D && (D == 64 || D == 128), op, ": qkv too narrow / head_dim 64 or 128");
+  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, "qkv alignment");
+  check_rope(cos, sin, pos, T, S, D);
+  check_fp8_cache(kc, k_scale, qkv, op, "k cache");
+  check_fp8_cache(vc, v_scale, qkv, op, "v cache");
+  TORCH_CHECK(kc.size(2) == hkv && kc.size(3) == D && vc.sizes() == kc.sizes(), op, ": caches must be [B, L, hkv, D]");
+  TORCH_CHECK(tpr >= 1 && T % tpr == 0 && T / tpr == kc.size(0), op, ": T = B * tokens-per-row");
+  TORCH_CHECK(kc.size(1) <= INT32_MAX && hq >= 0 && hkv >= 1, op, ": dims");
+  auto q = at::empty({T, hq, D}, qkv.options());
+  grt::RopeAppendFp8Params a{};
+  a.qkv = qkv.data_ptr(); a.ld = ld; a.q_out = q.data_ptr(); a.k_out = nullptr;
+  if (k_out.has_value()) {
+    check_contig(*k_out, "k_out");
+    TORCH_CHECK(k_out->scalar_type() == at::kBFloat16 && k_out->numel() == T * hkv * D && k_out->device() == qkv.device() &&
+                    reinterpret_cast<uintptr_t>(k_out->data_ptr()) % 16 == 0,
+                op, ": k_out must be a contiguous bf16 [T, hkv, D]");
+    a.k_out = k_out->data_ptr();
+  }
+  a.kc = kc.data_ptr(); a.vc = vc.data_ptr(); a.k_scale = k_scale.data_ptr<float>(); a.v_scale = v_scale.data_ptr<float>();
+  a.c_bs = kc.stride(0); a.c_ss = kc.stride(1); a.c_hs = kc.stride(2);
+  a.v_bs = vc.stride(0); a.v_ss = vc.stride(1); a.v_hs = vc.stride(2);
+  a.ks_bs = k_scale.stride(0); a.ks_ss = k_scale.stride(1); a.ks_hs = k_scale.stride(2);
+  a.vs_bs = v_scale.stride(0); a.vs_ss = v_scale.stride(1); a.vs_hs = v_scale.stride(2);
+  a.cos = cos.data_ptr<float>(); a.sin = sin.data_ptr<float>(); a.pos = pos.data_ptr<int32_t>();
+  a.T = T; a.tpr = (int)tpr; a.S = (int)S; a.L = (int)kc.size(1); a.hq = (int)hq; a.hkv = (int)hkv; a.D = (int)D;
+  grt::rope_append_fp8(a, cur_stream(qkv));
+  return q;
+}
+
+// rows [0, n) of an fp8 cache as bf16 [B, n, Hkv, D]
+Tensor kv_fp8_dequant(const Tensor& codes, const Tensor& scale, int64_t n) {
+  check_fp8_cache(codes, scale, codes, "kv_fp8_dequant", "cache");
+  TORCH_CHECK(n >= 0 && n <= codes.size(1) && codes.size(3) % 8 == 0 && codes.size(1) <= INT32_MAX, "kv_fp8_dequant: n / head_dim");
+  c10::OptionalDeviceGuard g(codes.device());
+  auto out = at::empty({codes.size(0), n, codes.size(2), codes.size(3)}, codes.options().dtype(at::kBFloat16));
+  grt::kv_fp8_dequant(codes.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), codes.stride(0), codes.stride(1),
+                      codes.stride(2), scale.stride(0), scale.stride(1), scale.stride(2), codes.size(0), (int)n,
+                      (int)codes.size(2), (int)codes.size(3), cur_stream(codes));
+  return out;
+}
+
 void rope_bwd(const Tensor& dq, const Tensor& dk, Tensor& dqkv, const Tensor& cos, const Tensor& sin,
               const optional<Tensor>& pos, int64_t hq, int64_t hkv, int64_t D, int64_t S) {
   check_contig(dq, "dq");
@@ -1154,6 +1221,70 @@ Tensor attn_decode_multi_d64(const Tensor& q, const Tensor& k, const Tensor& v, 
   return attn_decode_impl(q, k, v, seqlens_k, scale, 64, "attn_decode_multi_d64", nullptr, true);
 }
 
+// Decode attention over an fp8 cache (attn_decode_split_kernel with uint8 cache elements): q bf16
+// [B, T, Hq, D], T in 1..4; k / v codes with their scales; same split plan and token rule as above.
+Tensor attn_decode_fp8_impl(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& k_scale,
+                            const Tensor& v_scale, const optional<Tensor>& seqlens_k, double scale, int64_t D,
+                            const char* op) {
+  check_cuda(q, "q");
+  TORCH_CHECK(q.dim() == 4 && q.scalar_type() == at::kBFloat16 && q.stride(3) == 1, op, ": q must be bf16 [B, T, Hq, D]");
+  check_fp8_cache(k, k_scale, q, op, "k");
+  check_fp8_cache(v, v_scale, q, op, "v");
+  TORCH_CHECK(q.size(3) == D && k.size(3) == D && v.size(3) == D, op, ": head_dim ", D);
+  const int64_t T = q.size(1);
+  TORCH_CHECK(T >= 1 && T <= 4, op, ": 1 to 4 query tokens per sequence, got ", T);
+  TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0), op, ": k/v shapes");
+  const int64_t Hq = q.size(2), Hkv = k.size(2);
+  TORCH_CHECK(Hq % Hkv == 0, op, ": Hq % Hkv");
+  const int64_t G = Hq / Hkv;
+  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, op, ": GQA group must be 1, 2, 4 or 8");
+  TORCH_CHECK(q.stride(0) % 8 == 0 && q.stride(1) % 8 == 0 && q.stride(2) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              op, ": q strides must keep 16-byte alignment");
+  TORCH_CHECK(k.size(1) >= 1 && k.size(1) <= INT32_MAX && q.size(0) * T * Hq <= INT32_MAX, op, ": dims");
+  c10::OptionalDeviceGuard g(q.device());
+  grt::AttnDecodeParams p{};
+  p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr();
+  p.k_scale = k_scale.data_ptr<float>(); p.v_scale = v_scale.data_ptr<float>();
+  auto o = at::empty(q.sizes(), q.options());
+  p.o = o.data_ptr();
+  p.q_bs = q.stride(0); p.q_hs = q.stride(2);
+  p.k_bs = k.stride(0); p.k_ss = k.stride(1); p.k_hs = k.stride(2);
+  p.v_bs = v.stride(0); p.v_ss = v.stride(1); p.v_hs = v.stride(2);
+  p.ksc_bs = k_scale.stride(0); p.ksc_ss = k_scale.stride(1); p.ksc_hs = k_scale.stride(2);
+  p.vsc_bs = v_scale.stride(0); p.vsc_ss = v_scale.stride(1); p.vsc_hs = v_scale.stride(2);
+  p.o_bs = o.stride(0); p.o_hs = o.stride(2);
+  p.T = (int)T; p.q_ts = q.stride(1); p.o_ts = o.stride(1);
+  p.B = (int)q.size(0); p.Hq = (int)Hq; p.Hkv = (int)Hkv; p.Sk = (int)k.size(1);
+  p.NS = grt::attn_decode_splits(p.B, p.Hkv, p.Sk, (int)D);
+  p.seqlens_k = nullptr;
+  if (seqlens_k.has_value()) {
+    check_contig(*seqlens_k, "seqlens_k");
+    TORCH_CHECK(seqlens_k->scalar_type() == at::kInt && seqlens_k->numel() == q.size(0) &&
+                    seqlens_k->device() == q.device(),
+                op, ": seqlens_k int32 [B] on q's device");
+    p.seqlens_k = seqlens_k->data_ptr<int32_t>();
+  }
+  p.scale_log2 = (float)(scale * 1.4426950408889634);
+  const int64_t rows = (int64_t)p.B * T * Hq;
+  auto ws = at::empty({rows * p.NS * (D + 2)}, q.options().dtype(at::kFloat));
+  p.part_o = ws.data_ptr<float>();
+  p.part_m = p.part_o + rows * p.NS * D;
+  p.part_l = p.part_m + rows * p.NS;
+  grt::attn_decode_fp8(p, (int)D, cur_stream(q));
+  return o;
+}
+
+Tensor attn_decode_fp8(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& k_scale, const Tensor& v_scale,
+                       const optional<Tensor>& seqlens_k, double scale) {
+  return attn_decode_fp8_impl(q, k, v, k_scale, v_scale, seqlens_k, scale, 128, "attn_decode_fp8");
+}
+
+Tensor attn_decode_fp8_d64(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& k_scale,
+                           const Tensor& v_scale, const optional<Tensor>& seqlens_k, double scale) {
+  return attn_decode_fp8_impl(q, k, v, k_scale, v_scale, seqlens_k, scale, 64, "attn_decode_fp8_d64");
+}
+
 // test support: attn_decode_d64 plus its per-split partial states, [o, part_o [B, Hq, NS, 64],
 // part_m [B, Hq, NS] (log2 units), part_l [B, Hq, NS]]; the partials are written only when NS > 1
 std::vector<Tensor> attn_decode_d64_partials(const Tensor& q, const Tensor& k, const Tensor& v,
@@ -1818,6 +1949,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_fwd", &rope_fwd);
   m.def("rope_bwd", &rope_bwd);
   m.def("rope_append", &rope_append);
+  m.def("rope_append_fp8", &rope_append_fp8, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("hq"),
+        py::arg("hkv"), py::arg("D"), py::arg("S"), py::arg("kc"), py::arg("vc"), py::arg("k_scale"), py::arg("v_scale"),
+        py::arg("tpr"), py::arg("k_out") = py::none());
+  m.def("kv_fp8_dequant", &kv_fp8_dequant);
   m.def("scale_add_pe", &scale_add_pe);
   m.def("dropout_fwd", &dropout_fwd);
   m.def("dropout_bwd", &dropout_bwd);
@@ -1917,6 +2052,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_multi_d64", &attn_decode_multi_d64);
   m.def("attn_decode", &attn_decode);
   m.def("attn_decode_d64", &attn_decode_d64);
+  m.def("attn_decode_fp8", &attn_decode_fp8);
+  m.def("attn_decode_fp8_d64", &attn_decode_fp8_d64);
   m.def("attn_decode_d64_partials", &attn_decode_d64_partials,
         "test support: attn_decode_d64 and its per-split (o, max, sum) partial states");
   m.def("embedding_fwd", &embedding_fwd);

@@ -61,6 +61,22 @@ void rope_append(const void* qkv, int64_t ld, void* q_out, void* kc, void* vc, i
 void rope_bwd(DType dt, const void* dq, const void* dk, void* dqkv, int64_t ld, const float* cos,
               const float* sin, const int32_t* pos, int64_t T, int S, int hq, int hkv, int D,
               hipStream_t s);
+// fp8 KV cache (kv_fp8.hip; format: ops/_ref.py::kv_fp8_quantize, grt_fp8.h). rope_append_fp8 is
+// rope_append with a quantising cache write: kc / vc hold e4m3fn codes (uint8 [B, L, hkv, D]),
+// k_scale / v_scale one fp32 per (batch, slot, kv head); the rotated K is rounded to bf16 before
+// it is quantised, and k_out (may be null, bf16 [T, hkv, D]) receives that bf16 value.
+struct RopeAppendFp8Params {
+  const void* qkv; int64_t ld; void* q_out; void* k_out;
+  void* kc; void* vc; float* k_scale; float* v_scale;
+  int64_t c_bs, c_ss, c_hs, v_bs, v_ss, v_hs;        // code strides (bytes = elements)
+  int64_t ks_bs, ks_ss, ks_hs, vs_bs, vs_ss, vs_hs;  // scale strides (elements)
+  const float* cos; const float* sin; const int32_t* pos;
+  int64_t T; int tpr, S, L, hq, hkv, D;
+};
+void rope_append_fp8(const RopeAppendFp8Params& a, hipStream_t s);
+// out (bf16 [B, n, H, D] contiguous) = dequantised cache rows [0, n)
+void kv_fp8_dequant(const void* codes, const float* scale, void* out, int64_t c_bs, int64_t c_ss, int64_t c_hs,
+                    int64_t s_bs, int64_t s_ss, int64_t s_hs, int64_t B, int n, int H, int D, hipStream_t s);
 // out = emb * scale + pe[t % S]   (BasicLLM input path; pe may be null)
 void scale_add_pe(DType dt, const void* emb, const float* pe, void* out, int64_t T, int S, int d,
                   float scale, hipStream_t s);
@@ -240,7 +256,8 @@ struct AttnBwdParams {
 };
 void attn_bwd(const AttnBwdParams& p, hipStream_t s);
 int64_t attn_bwd_workspace_floats(int B, int Hq, int Sq, int D);
-// decode split-K attention (decode_attention.hip): bf16, Hq / Hkv in {1,2,4,8}, head_dim 128 or 64,
+// decode split-K attention (decode_attention.hip): bf16 (attn_decode_fp8: an fp8 cache of codes and
+// scales), Hq / Hkv in {1,2,4,8}, head_dim 128 or 64,
 // T = 1 query token per sequence (the decode step) or T in 2..4 whose keys are the last T of the row
 // (verify step of speculative decoding): token t attends keys [0, seqlens_k[b] - (T - 1 - t)).
 // NS = attn_decode_splits(.., head_dim), workspace B * T * Hq * NS * (head_dim + 2) floats (unused
@@ -255,9 +272,14 @@ struct AttnDecodeParams {
   // T query tokens per sequence, always set: q / o are [B, T, Hq, D] with token strides q_ts /
   // o_ts, o contiguous
   int T; int64_t q_ts, o_ts;
+  // fp8 cache (attn_decode_fp8 only): k / v are e4m3fn codes (uint8, strides in bytes, 8-byte
+  // aligned) with one fp32 scale per (batch, key slot, kv head)
+  const float* k_scale; const float* v_scale;
+  int64_t ksc_bs, ksc_ss, ksc_hs, vsc_bs, vsc_ss, vsc_hs;
 };
 int attn_decode_splits(int B, int Hkv, int Sk, int head_dim = 128);
 void attn_decode(const AttnDecodeParams& p, int head_dim, hipStream_t s);
+void attn_decode_fp8(const AttnDecodeParams& p, int head_dim, hipStream_t s);
 // exact-fp32 variants (attention_f32.hip): same params with fp32 tensors, head_dim 64 or 128
 bool attn_f32_supported(int head_dim);
 void attn_fwd_f32(const AttnParams& p, hipStream_t s);

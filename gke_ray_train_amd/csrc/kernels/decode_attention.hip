@@ -1,4 +1,4 @@
-// Split-K attention for the decode step, bf16, head_dim 128 or 64: one new query token per sequence,
+// Split-K attention for the decode step, bf16 (or an fp8 cache, below), head_dim 128 or 64: one new query token per sequence,
 // or the 2-4 query tokens of a speculative verify step.
 //
 // Reference role: the KV-cache decode of HF ``generate`` in the inference comparison
@@ -30,7 +30,18 @@
 // more than the 512-register file of a 256-thread workgroup holds without scratch, so those two
 // cases run TT = 2 tokens per workgroup and tile the tokens over blockIdx.z (K / V are then read
 // twice). Partials are [B, T, Hq, NS].
+//
+// The kernel is last a template on KT, the cache element: bf16, or uint8_t for the fp8 cache (OCP
+// e4m3fn codes with one fp32 scale per (key, kv head); kv_fp8.hip writes it). The lane mapping is
+// the same, so K and V are one 8-byte load per lane, converted by v_cvt_pk_f32_fp8; the two scales
+// of a key are loaded by all its lanes from one address and prefetched with the codes. The K scale
+// multiplies the score after the lane reduction and the V scale the weight e of the key before
+// the output FMAs (the sum l keeps e itself), so no element is scaled on its own. All of it is
+// behind the compile-time KT: the bf16 instantiations carry none of it.
+#include <type_traits>
+
 #include "grt_common.h"
+#include "grt_fp8.h"
 #include "grt_kernels.h"
 
 namespace grt {
@@ -38,8 +49,10 @@ namespace {
 
 // Everything that exists only for TT > 1 (token tile, per-row key limit, token terms of the
 // addresses) is behind the compile-time TT, so TT = 1 carries none of it.
-template <int D, int G, int TT>
+template <int D, int G, int TT, typename KT>
 __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecodeParams p) {
+  constexpr bool kFp8 = sizeof(KT) == 1;
+  using Raw = std::conditional_t<kFp8, uint2, u32x4>;  // 8 cache elements of a lane
   constexpr int kLanes = D / 8;           // lanes per key
   constexpr int kWaveKeys = 64 / kLanes;  // keys per wave per step
   constexpr int kStep = 4 * kWaveKeys;    // keys per workgroup per step
@@ -56,15 +69,26 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
   const int per = ((len + p.NS - 1) / p.NS + kStep - 1) / kStep * kStep;
   const int k0 = split * per, k1 = min(len, k0 + per);
 
-  const bf16* Kb = (const bf16*)p.k + (int64_t)b * p.k_bs + (int64_t)hkv * p.k_hs + c * 8;
-  const bf16* Vb = (const bf16*)p.v + (int64_t)b * p.v_bs + (int64_t)hkv * p.v_hs + c * 8;
+  const KT* Kb = (const KT*)p.k + (int64_t)b * p.k_bs + (int64_t)hkv * p.k_hs + c * 8;
+  const KT* Vb = (const KT*)p.v + (int64_t)b * p.v_bs + (int64_t)hkv * p.v_hs + c * 8;
+  [[maybe_unused]] const float* Ksb = nullptr;
+  [[maybe_unused]] const float* Vsb = nullptr;
+  [[maybe_unused]] float ksn = 0.f, vsn = 0.f;  // the scales of the key in kraw / vraw
+  if constexpr (kFp8) {
+    Ksb = p.k_scale + (int64_t)b * p.ksc_bs + (int64_t)hkv * p.ksc_hs;
+    Vsb = p.v_scale + (int64_t)b * p.vsc_bs + (int64_t)hkv * p.vsc_hs;
+  }
   // the K / V stream is pipelined one step ahead, and its first loads are issued before the query
   // loads, so the two dependent round trips at the start overlap (most splits are 1-2 steps long)
   int j = k0 + wave * kWaveKeys + grp;
-  u32x4 kraw{}, vraw{};
+  Raw kraw{}, vraw{};
   if (j < k1) {
-    kraw = *reinterpret_cast<const u32x4*>(Kb + (int64_t)j * p.k_ss);
-    vraw = *reinterpret_cast<const u32x4*>(Vb + (int64_t)j * p.v_ss);
+    kraw = *reinterpret_cast<const Raw*>(Kb + (int64_t)j * p.k_ss);
+    vraw = *reinterpret_cast<const Raw*>(Vb + (int64_t)j * p.v_ss);
+    if constexpr (kFp8) {
+      ksn = Ksb[(int64_t)j * p.ksc_ss];
+      vsn = Vsb[(int64_t)j * p.vsc_ss];
+    }
   }
   float q[R][8];
   int rlen[TT];  // TT > 1: keys token t0 + tt sees; 0 for a token past T (last tile of an uneven tiling)
@@ -89,11 +113,21 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
   }
   for (; j < k1; j += kStep) {
     float kf[8], vf[8];
-    bf16x8_to_f32(kraw, kf);
-    bf16x8_to_f32(vraw, vf);
+    [[maybe_unused]] const float ks = ksn, vs = vsn;
+    if constexpr (kFp8) {
+      fp8x8_to_f32(kraw.x, kraw.y, kf);
+      fp8x8_to_f32(vraw.x, vraw.y, vf);
+    } else {
+      bf16x8_to_f32(kraw, kf);
+      bf16x8_to_f32(vraw, vf);
+    }
     if (j + kStep < k1) {
-      kraw = *reinterpret_cast<const u32x4*>(Kb + (int64_t)(j + kStep) * p.k_ss);
-      vraw = *reinterpret_cast<const u32x4*>(Vb + (int64_t)(j + kStep) * p.v_ss);
+      kraw = *reinterpret_cast<const Raw*>(Kb + (int64_t)(j + kStep) * p.k_ss);
+      vraw = *reinterpret_cast<const Raw*>(Vb + (int64_t)(j + kStep) * p.v_ss);
+      if constexpr (kFp8) {
+        ksn = Ksb[(int64_t)(j + kStep) * p.ksc_ss];
+        vsn = Vsb[(int64_t)(j + kStep) * p.vsc_ss];
+      }
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -102,14 +136,21 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const AttnDecode
       for (int i = 0; i < 8; ++i) s = fmaf(q[r][i], kf[i], s);
 #pragma unroll
       for (int off = kLanes / 2; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+      if constexpr (kFp8) s *= ks;
       // one token sees every key of its split; the limit of a row of several is uniform over the
       // lanes of a key, and the shuffles above stay outside it
       if (TT == 1 || j < rlen[r / G]) {
         const float mn = fmaxf(m[r], s);
         const float a = fast_exp2(m[r] - mn), e = fast_exp2(s - mn);
         l[r] = l[r] * a + e;
+        if constexpr (kFp8) {
+          const float ev = e * vs;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) o[r][i] = fmaf(o[r][i], a, e * vf[i]);
+          for (int i = 0; i < 8; ++i) o[r][i] = fmaf(o[r][i], a, ev * vf[i]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) o[r][i] = fmaf(o[r][i], a, e * vf[i]);
+        }
         m[r] = mn;
       }
     }
@@ -201,31 +242,31 @@ __global__ __launch_bounds__(D) void attn_decode_combine_kernel(const AttnDecode
   *op = static_cast<bf16>(ll > 0.f ? oo / ll : 0.f);
 }
 
-template <int D, int G, int TT>
+template <int D, int G, int TT, typename KT>
 void launch_split(const AttnDecodeParams& p, hipStream_t s) {
   const dim3 grid((unsigned)(p.B * p.Hkv), (unsigned)p.NS, (unsigned)((p.T + TT - 1) / TT));
-  hipLaunchKernelGGL((attn_decode_split_kernel<D, G, TT>), grid, dim3(256), 0, s, p);
+  hipLaunchKernelGGL((attn_decode_split_kernel<D, G, TT, KT>), grid, dim3(256), 0, s, p);
 }
 
-template <int D, int G>
+template <int D, int G, typename KT>
 void launch_tokens(const AttnDecodeParams& p, hipStream_t s) {
-  if (p.T == 1) return launch_split<D, G, 1>(p, s);
+  if (p.T == 1) return launch_split<D, G, 1, KT>(p, s);
   if constexpr (G == 8) {
-    launch_split<D, 8, 2>(p, s);  // T = 3, 4: two token tiles (see above)
+    launch_split<D, 8, 2, KT>(p, s);  // T = 3, 4: two token tiles (see above)
   } else {
-    if (p.T == 2) launch_split<D, G, 2>(p, s);
-    else if (p.T == 3) launch_split<D, G, 3>(p, s);
-    else launch_split<D, G, 4>(p, s);
+    if (p.T == 2) launch_split<D, G, 2, KT>(p, s);
+    else if (p.T == 3) launch_split<D, G, 3, KT>(p, s);
+    else launch_split<D, G, 4, KT>(p, s);
   }
 }
 
-template <int D>
+template <int D, typename KT>
 void launch_decode(const AttnDecodeParams& p, hipStream_t s) {
   switch (p.Hq / p.Hkv) {
-    case 1: launch_tokens<D, 1>(p, s); break;
-    case 2: launch_tokens<D, 2>(p, s); break;
-    case 4: launch_tokens<D, 4>(p, s); break;
-    default: launch_tokens<D, 8>(p, s); break;
+    case 1: launch_tokens<D, 1, KT>(p, s); break;
+    case 2: launch_tokens<D, 2, KT>(p, s); break;
+    case 4: launch_tokens<D, 4, KT>(p, s); break;
+    default: launch_tokens<D, 8, KT>(p, s); break;
   }
   if (D == 64 && p.NS == 1) return;  // the split kernel wrote the output itself
   // the combine kernel sees [B * T] sequences of one token: (b, t) is its batch index (with T = 1
@@ -257,8 +298,13 @@ int attn_decode_splits(int B, int Hkv, int Sk, int head_dim) {
 }
 
 void attn_decode(const AttnDecodeParams& p, int head_dim, hipStream_t s) {
-  if (head_dim == 64) launch_decode<64>(p, s);
-  else launch_decode<128>(p, s);
+  if (head_dim == 64) launch_decode<64, bf16>(p, s);
+  else launch_decode<128, bf16>(p, s);
+}
+
+void attn_decode_fp8(const AttnDecodeParams& p, int head_dim, hipStream_t s) {
+  if (head_dim == 64) launch_decode<64, uint8_t>(p, s);
+  else launch_decode<128, uint8_t>(p, s);
 }
 
 }  // namespace grt

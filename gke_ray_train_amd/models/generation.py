@@ -41,6 +41,22 @@ read per ``sync_every`` of them. The slots of rejected drafts lie past the valid
 rewritten by the next step; a finished or full row is inert. ``ops/_ref.py::prompt_lookup_draft``
 and ``::spec_accept`` are the host implementations, which the host loops (``device_loop=False``,
 ``use_graph=False``) run on the logits [T, V] of the same step.
+
+fp8 KV cache (``generate(..., kv_cache_dtype="fp8")``, ``KVCache(..., "fp8")``): K and V are stored
+as OCP e4m3fn codes with one fp32 scale per (token, kv head) (``ops/_ref.py::kv_fp8_quantize`` is
+the definition), (D + 4) / 2D of the bf16 cache's bytes. ``rope_append_fp8`` (kv_fp8.hip) rotates
+K, rounds it to bf16 (the value the bf16 cache would hold) and quantises it and V on the way in;
+the split-K decode kernel reads the codes directly (``ops.decode_attention_fp8``, T = 1..4 tokens).
+The prefill of an empty cache fills the cache the same way but attends over the fresh bf16 K / V,
+so its logits are bitwise those of the bf16 cache. DECODE TOKENS ATTEND TO THEIR OWN K / V AS
+STORED, that is, quantised: a token's key and value are written before its attention runs, and
+the kernel reads nothing but the cache. In the captured one-token step the qkv GEMV runs without
+its RoPE / append epilogue and ``rope_append_fp8`` follows it: one launch per layer more than the
+bf16 step. A chunk of more than 4 tokens on a non-empty cache (chunked prefill) is a slow path:
+append, dequantise rows [0, n) to bf16 (``kv_fp8_dequant``) and run the flash kernel. Without the
+HIP kernels (CPU, fp32 model, other head dims) the cache is quantised by ``_ref`` and attention
+runs over the dequantised rows. There is no flash-kernel decode path for the fp8 cache:
+``GRT_DECODE_ATTN=0`` with it is refused wherever it would run on those kernels.
 """
 from __future__ import annotations
 
@@ -54,9 +70,44 @@ from .. import _native, ops
 from ..ops import _ref
 
 
+KV_CACHE_DTYPES = (None, "auto", "fp8", "fp8_e4m3")
+
+
+def _kv_dtype(model, kv_cache_dtype):
+    """``KVCache``'s dtype argument for a ``kv_cache_dtype`` choice: the model's dtype or "fp8"."""
+    if kv_cache_dtype not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype must be one of {KV_CACHE_DTYPES}, got {kv_cache_dtype!r}")
+    return "fp8" if kv_cache_dtype in ("fp8", "fp8_e4m3") else _cache_dtype(model)
+
+
+def _fp8_kernels_ok(is_cuda: bool, dtype, D: int) -> bool:
+    """The fp8 cache runs on the HIP kernels (``rope_append_fp8``, fp8 decode attention): a bf16 model
+    on the GPU with head_dim 128 or 64. Anything else quantises with ``_ref``."""
+    return is_cuda and dtype == torch.bfloat16 and D in (64, 128) and _native.kernels_available()
+
+
+def _check_fp8_decode(fp8: bool, is_cuda: bool, dtype, D: int) -> None:
+    """``GRT_DECODE_ATTN=0`` sends decode attention to the flash kernel, which cannot read fp8 codes:
+    refused wherever the fp8 cache would run on the kernels (the ``_ref`` path has no such kernel)."""
+    from ..ops import fused
+    if fp8 and not fused._DECODE_KERNEL and _fp8_kernels_ok(is_cuda, dtype, D):
+        raise ValueError("kv_cache_dtype='fp8' with GRT_DECODE_ATTN=0: the fp8 KV cache is read by the split-K decode "
+                         "kernel only, there is no flash-kernel decode path for it")
+
+
 class KVCache:
+    """``dtype`` a torch dtype, or "fp8": k / v are then uint8 e4m3fn codes [B, max_len, Hkv, D] and
+    ``k_scale`` / ``v_scale`` hold one fp32 scale per (row, slot, kv head) (see module doc)."""
+
     def __init__(self, cfg, B, max_len, device, dtype):
         hd, hkv = cfg.head_dim, cfg.num_key_value_heads
+        self.fp8 = isinstance(dtype, str)
+        if self.fp8:
+            if dtype not in ("fp8", "fp8_e4m3"):
+                raise ValueError(f"KVCache: dtype must be a torch dtype or 'fp8', got {dtype!r}")
+            dtype = torch.uint8
+            self.k_scale, self.v_scale = ([torch.zeros(B, max_len, hkv, device=device, dtype=torch.float32)
+                                           for _ in range(cfg.num_hidden_layers)] for _ in range(2))
         self.k = [torch.zeros(B, max_len, hkv, hd, device=device, dtype=dtype) for _ in range(cfg.num_hidden_layers)]
         self.v = [torch.zeros(B, max_len, hkv, hd, device=device, dtype=dtype) for _ in range(cfg.num_hidden_layers)]
         self.len = 0
@@ -64,6 +115,11 @@ class KVCache:
         # per-row token counts [B] int32 after a masked (ragged) prefill; ``len`` is then the longest
         # row's, which is what the fullness checks compare with ``max_len``
         self.lens: Optional[torch.Tensor] = None
+
+    def nbytes(self) -> int:
+        """Bytes held by the cache tensors (codes and scales of an fp8 cache)."""
+        ts = self.k + self.v + ((self.k_scale + self.v_scale) if self.fp8 else [])
+        return sum(t.numel() * t.element_size() for t in ts)
 
 
 @dataclass
@@ -141,6 +197,8 @@ def _eager_attention(attn, qkv, B, S, pos0, cos, sin, cache: KVCache, li: int, r
     cache slot row_pos[b]; without it the S tokens of every row sit at pos0 ... pos0 + S - 1."""
     hq, hkv, D = attn.hq, attn.hkv, attn.hd
     pos = row_pos if row_pos is not None else torch.arange(pos0, pos0 + S, device=qkv.device, dtype=torch.int32).repeat(B)
+    if cache.fp8:
+        return _eager_attention_fp8(attn, qkv, B, S, pos0, cos, sin, cache, li, row_pos, pos)
     if _fused_ok(qkv, cache, li):
         # RoPE of q / k and the cache append of k / v in one kernel (rope_append, elementwise.hip)
         q = _native.kernels().rope_append(qkv.contiguous(), cos, sin, pos, hq, hkv, D, cos.shape[0],
@@ -166,11 +224,69 @@ def _eager_attention(attn, qkv, B, S, pos0, cos, sin, cache: KVCache, li: int, r
     return o.reshape(B * S, hq * D)
 
 
+def _fp8_append(K, qkv, cos, sin, pos, hq, hkv, D, cache: KVCache, li: int, tpr: int, k_out=None):
+    """q [M, hq, D] rotated; K (rotated, rounded to bf16) and V quantised into the fp8 cache."""
+    return K.rope_append_fp8(qkv.contiguous(), cos, sin, pos, hq, hkv, D, cos.shape[0], cache.k[li], cache.v[li],
+                             cache.k_scale[li], cache.v_scale[li], tpr, k_out=k_out)
+
+
+def _eager_attention_fp8(attn, qkv, B, S, pos0, cos, sin, cache: KVCache, li: int, row_pos, pos):
+    """``_eager_attention`` over an fp8 cache (see module doc): the prefill of an empty cache
+    attends over the fresh unquantised K / V; every later call attends over the cache as stored."""
+    hq, hkv, D = attn.hq, attn.hkv, attn.hd
+    n = pos0 + S
+    prefill = pos0 == 0 and row_pos is None
+    lens = row_pos + 1 if row_pos is not None else None
+    x4 = qkv.view(B, S, hq + 2 * hkv, D)
+    if _fp8_kernels_ok(qkv.is_cuda, qkv.dtype, D):
+        _check_fp8_decode(True, True, qkv.dtype, D)  # a direct forward_cached obeys the switch too
+        K = _native.kernels()
+        k_out = torch.empty(B * S, hkv, D, device=qkv.device, dtype=qkv.dtype) if prefill else None
+        q = _fp8_append(K, qkv, cos, sin, pos, hq, hkv, D, cache, li, S, k_out).view(B, S, hq, D)
+        if prefill:
+            o = ops.flash_attention(q, k_out.view(B, S, hkv, D), x4[:, :, hq + hkv:], causal=True)
+        elif S <= 4:
+            o = ops.decode_attention_fp8(q, cache.k[li][:, :n], cache.v[li][:, :n], cache.k_scale[li][:, :n],
+                                         cache.v_scale[li][:, :n], seqlens_k=lens)
+        else:  # chunked prefill, the slow path: a bf16 copy of the rows so far for the flash kernel
+            kk = K.kv_fp8_dequant(cache.k[li], cache.k_scale[li], n)
+            vv = K.kv_fp8_dequant(cache.v[li], cache.v_scale[li], n)
+            o = ops.flash_attention(q, kk, vv, causal=True)
+        return o.reshape(B * S, hq * D)
+    x3 = qkv.view(B * S, hq + 2 * hkv, D)
+    q = _ref.apply_rope(x3[:, :hq], cos, sin, pos).view(B, S, hq, D)
+    k = _ref.apply_rope(x3[:, hq:hq + hkv], cos, sin, pos).view(B, S, hkv, D)
+    v = x4[:, :, hq + hkv:]
+    (kq, ks), (vq, vs) = _ref.kv_fp8_quantize(k), _ref.kv_fp8_quantize(v)
+    if row_pos is None:
+        cache.k[li][:, pos0:n], cache.k_scale[li][:, pos0:n] = kq, ks
+        cache.v[li][:, pos0:n], cache.v_scale[li][:, pos0:n] = vq, vs
+    else:
+        b, slot = torch.arange(B, device=qkv.device), row_pos.long()
+        cache.k[li][b, slot], cache.k_scale[li][b, slot] = kq[:, 0], ks[:, 0]
+        cache.v[li][b, slot], cache.v_scale[li][b, slot] = vq[:, 0], vs[:, 0]
+    if prefill:
+        kk, vv = k, v
+    else:
+        kk = _ref.kv_fp8_dequantize(cache.k[li][:, :n], cache.k_scale[li][:, :n], qkv.dtype)
+        vv = _ref.kv_fp8_dequantize(cache.v[li][:, :n], cache.v_scale[li][:, :n], qkv.dtype)
+    if row_pos is None:
+        o = ops.flash_attention(q, kk, vv, causal=True)
+    else:
+        o = ops.flash_attention(q, kk, vv, causal=False, seqlens_k=lens)
+    return o.reshape(B * S, hq * D)
+
+
 def _device_attention(attn, qkv, B, T, cos, sin, cache: KVCache, li: int, pos_b, lens):
     """The captured step's middle, every position read from device tensors: T tokens per row at
     positions and cache slots pos_b [B * T] (rows differ after a masked prefill), the last T of the
     row's ``lens`` valid keys. ``T`` > 1 is the verify step of speculative decoding."""
     hq, hkv, D = attn.hq, attn.hkv, attn.hd
+    if cache.fp8:
+        q = _fp8_append(_native.kernels(), qkv, cos, sin, pos_b, hq, hkv, D, cache, li, T)
+        o = ops.decode_attention_fp8(q.view(B, T, hq, D), cache.k[li], cache.v[li], cache.k_scale[li],
+                                     cache.v_scale[li], seqlens_k=lens)
+        return o.reshape(B * T, hq * D)
     q = _native.kernels().rope_append(qkv.contiguous(), cos, sin, pos_b, hq, hkv, D, cos.shape[0],
                                       cache.k[li], cache.v[li], T)
     if T == 1:
@@ -295,18 +411,27 @@ def _fused_norm_layer_step(layer, h, first: bool, ws: _NormWorkspace, B, cos, si
     down_proj write h = y + residual and add sum(h^2) to a fixed-point accumulator, qkv / gate_up
     normalise their input on the fly from (h, accumulator, norm weight), and the qkv epilogue
     rotates q / k and appends k / v to the cache. ``h`` IS the residual stream between
-    layers; slot 0 carries the post-attention norm's statistics, slot 1 the next input norm's."""
+    layers; slot 0 carries the post-attention norm's statistics, slot 1 the next input norm's.
+    With an fp8 cache the qkv GEMV has no epilogue (its norm-on-load stays) and ``rope_append_fp8``
+    follows it, one more launch per layer; the fp8 decode kernel then reads the cache."""
     K = _native.kernels()
     attn, mlp = layer.self_attn, layer.mlp
     ln1, ln2 = layer.input_layernorm, layer.post_attention_layernorm
     hq, hkv, D = attn.hq, attn.hkv, attn.hd
     # the qkv GEMV's epilogue applies RoPE and appends k / v to the cache (no rope_append launch)
-    rope = dict(cos=cos, sin=sin, pos=pos_b, kc=cache.k[li], vc=cache.v[li], hq=hq, hkv=hkv)
-    if first:  # layer 0: h is the embedding (no residual add, no producer GEMV summed its squares)
+    rope = {} if cache.fp8 else dict(cos=cos, sin=sin, pos=pos_b, kc=cache.k[li], vc=cache.v[li], hq=hq, hkv=hkv)
+    if first and cache.fp8:  # no norm-on-load and no epilogue: the plain GEMV
+        q = K.gemv(ops.rms_norm(h, ln1.weight, ln1.eps), attn.qkv_proj.weight)
+    elif first:  # layer 0: h is the embedding (no residual add, no producer GEMV summed its squares)
         q = K.gemv_fused(ops.rms_norm(h, ln1.weight, ln1.eps), attn.qkv_proj.weight, ws.sumsq, 1, **rope)
     else:
         q = K.gemv_fused(h, attn.qkv_proj.weight, ws.sumsq, 1, g=ln1.weight, eps=ln1.eps, **rope)
-    o = ops.flash_attention(q.view(B, 1, hq, D), cache.k[li], cache.v[li], causal=False, seqlens_k=lens)
+    if cache.fp8:  # q is the whole qkv row here
+        q = _fp8_append(K, q, cos, sin, pos_b, hq, hkv, D, cache, li, 1)
+        o = ops.decode_attention_fp8(q.view(B, 1, hq, D), cache.k[li], cache.v[li], cache.k_scale[li],
+                                     cache.v_scale[li], seqlens_k=lens)
+    else:
+        o = ops.flash_attention(q.view(B, 1, hq, D), cache.k[li], cache.v[li], causal=False, seqlens_k=lens)
     h = K.gemv_fused(o.reshape(B, hq * D), attn.o_proj.weight, ws.sumsq, 0, res=h)
     gu = K.gemv_fused(h, mlp.gate_up_proj.weight, ws.sumsq, 0, g=ln2.weight, eps=ln2.eps)
     return K.gemv_fused(gu, mlp.down_proj.weight, ws.sumsq, 1, swiglu=True, res=h)
@@ -363,11 +488,14 @@ class GraphDecoder:
     number and drafts for the next replay. ``n_replays`` / ``n_emitted`` count both. Without a
     sampler ``step_spec(ids, p)`` returns the logits [T, V] and the host does the rest.
 
+    ``kv_cache_dtype="fp8"`` stores the cache as e4m3fn codes (see module doc); every mode above
+    takes it.
+
     Needs a bf16 Llama on the GPU with head_dim 128 or 64 (the HIP RoPE epilogue / decode
     attention kernels)."""
 
     def __init__(self, model, B: int, max_len: int, sampler: Optional[SamplerConfig] = None,
-                 spec: Optional[SpecConfig] = None):
+                 spec: Optional[SpecConfig] = None, kv_cache_dtype=None):
         self.model = model
         self.spec = spec
         self.T = 1
@@ -382,7 +510,9 @@ class GraphDecoder:
         T = self.T
         self.n_replays = 0
         self.device = dev = next(model.parameters()).device
-        self.cache = KVCache(model.config, B, max_len, dev, _cache_dtype(model))
+        kv = _kv_dtype(model, kv_cache_dtype)
+        _check_fp8_decode(kv == "fp8", dev.type == "cuda", next(model.parameters()).dtype, model.config.head_dim)
+        self.cache = KVCache(model.config, B, max_len, dev, kv)
         self.B = B
         self.cos, self.sin = model.rope(max_len, dev)
         self.ids = torch.zeros(B, T, dtype=torch.long, device=dev)
@@ -615,13 +745,13 @@ last_spec_stats = {"n_replays": 0, "n_emitted": 0}  # of the latest speculative 
 
 
 def _spec_generate(model, input_ids, rows, P: int, sampler: SamplerConfig, spec: SpecConfig, graph: bool,
-                   on_device: bool, sync_every: int) -> torch.Tensor:
+                   on_device: bool, sync_every: int, kv=None) -> torch.Tensor:
     """The new tokens [n] of one sequence by prompt-lookup speculative decoding (see ``generate``)."""
     K, new = spec.num_tokens, sampler.max_new_tokens
     dev = input_ids.device
     max_len = P + new + K
     if on_device:
-        dec = GraphDecoder(model, 1, max_len, sampler=sampler, spec=spec)
+        dec = GraphDecoder(model, 1, max_len, sampler=sampler, spec=spec, kv_cache_dtype=kv)
         dec.first_token(dec.prefill(input_ids, rows))
         left = new - 1  # every replay of a live row emits at least one token
         while left > 0:
@@ -636,13 +766,13 @@ def _spec_generate(model, input_ids, rows, P: int, sampler: SamplerConfig, spec:
         return dec.out[0, :n]
     prompt = _row_prompt(input_ids, rows)
     if graph:
-        dec = GraphDecoder(model, 1, max_len, spec=spec)
+        dec = GraphDecoder(model, 1, max_len, spec=spec, kv_cache_dtype=kv)
         first = dec.prefill(input_ids, rows)
 
         def step(ids, p):
             return dec.step_spec(torch.tensor(ids, device=dev), p)
     else:
-        cache = KVCache(model.config, 1, max_len, dev, _cache_dtype(model))
+        cache = KVCache(model.config, 1, max_len, dev, _kv_dtype(model, kv))
         first = forward_cached(model, input_ids, cache, rows)
         cache.lens = None  # one row: nothing is ragged once its tokens sit at 0 ... P - 1
 
@@ -684,7 +814,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              top_p: Optional[float] = None, attention_mask=None, pad_token_id=None, generator=None,
              use_graph: Optional[bool] = None, sync_every: int = 16, top_k: Optional[int] = None,
              seed: Optional[int] = None, device_loop: Optional[bool] = None,
-             prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: int = 2, _spec_plan=None, **_):
+             prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: int = 2, _spec_plan=None,
+             kv_cache_dtype: Optional[str] = None, **_):
     """Returns [B, prompt + generated] token ids (HF ``generate`` output convention).
 
     ``attention_mask`` [B, S] (bool / integer, HF semantics) batches prompts of unequal length: row
@@ -729,11 +860,21 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     replays; the graph host loop and the eager path do them on the host. ``ValueError``: K outside
     1..3, N < 1, more than one sequence, a ``generator``, or prompt + ``max_new_tokens`` + K past
     ``max_position_embeddings``. ``_spec_plan`` is a private test hook (``SpecConfig.plan``).
-    ``last_spec_stats`` holds the verify steps and tokens of the latest such call."""
+    ``last_spec_stats`` holds the verify steps and tokens of the latest such call.
+
+    ``kv_cache_dtype``: ``None`` / ``"auto"`` keeps the cache in the model's dtype; ``"fp8"`` /
+    ``"fp8_e4m3"`` stores it as e4m3fn codes with one fp32 scale per (token, kv head), (D + 4) / 2D of
+    the bf16 bytes (see the module doc: the prefill logits are those of the bf16 cache, decode
+    tokens attend to the quantised cache, the captured one-token step has one more launch per
+    layer, a chunk of more than 4 tokens on a non-empty cache takes a dequantising slow path).
+    Every mode above takes it. ``ValueError``: another value, or ``GRT_DECODE_ATTN=0`` with the fp8
+    cache on the GPU."""
     was = model.training
     model.eval()
     try:
         B, S = input_ids.shape
+        kv = "fp8" if _kv_dtype(model, kv_cache_dtype) == "fp8" else None
+        _check_fp8_decode(kv == "fp8", input_ids.is_cuda, next(model.parameters()).dtype, model.config.head_dim)
         rows = _mask_rows(attention_mask, B, S)
         P = S if rows is None else max(rows.lens)  # the longest prompt: the cache holds P + max_new_tokens
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
@@ -773,21 +914,21 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
         on_device = can and (device_loop if device_loop is not None else _DEVICE_SAMPLER)
         if K and max_new_tokens >= 1:
             new = _spec_generate(model, input_ids, rows, P, sampler, SpecConfig(K, N, _spec_plan), graph, on_device,
-                                 sync_every)[None]
+                                 sync_every, kv)[None]
         elif on_device:
-            new = _device_loop(model, input_ids, rows, P, sampler, sync_every)
+            new = _device_loop(model, input_ids, rows, P, sampler, sync_every, kv)
         else:
-            new = _host_loop(model, input_ids, rows, P, sampler, graph, generator, sync_every)
+            new = _host_loop(model, input_ids, rows, P, sampler, graph, generator, sync_every, kv)
         return torch.cat([input_ids, new], 1)
     finally:
         if was:
             model.train()
 
 
-def _device_loop(model, input_ids, rows, P: int, sampler: SamplerConfig, sync_every: int) -> torch.Tensor:
+def _device_loop(model, input_ids, rows, P: int, sampler: SamplerConfig, sync_every: int, kv=None) -> torch.Tensor:
     """The new tokens [B, n] with the token picked inside the captured step."""
     new, eos = sampler.max_new_tokens, sampler.eos_ids
-    dec = GraphDecoder(model, input_ids.shape[0], P + new, sampler=sampler)
+    dec = GraphDecoder(model, input_ids.shape[0], P + new, sampler=sampler, kv_cache_dtype=kv)
     dec.first_token(dec.prefill(input_ids, rows))
     done = 1
     while done < new:
@@ -819,15 +960,15 @@ def _multinomial_pick(logits, temperature: float, top_k: int, top_p: float, gene
     return torch.multinomial(probs / probs.sum(-1, keepdim=True), 1, generator=generator).squeeze(-1)
 
 
-def _host_loop(model, input_ids, rows, P: int, c: SamplerConfig, graph: bool, generator, sync_every: int):
+def _host_loop(model, input_ids, rows, P: int, c: SamplerConfig, graph: bool, generator, sync_every: int, kv=None):
     """The new tokens [B, n], picked on the host from the logits of the graph's or the eager step."""
     B, new = input_ids.shape[0], c.max_new_tokens
     if graph:
-        dec = GraphDecoder(model, B, P + new)
+        dec = GraphDecoder(model, B, P + new, kv_cache_dtype=kv)
         logits = dec.prefill(input_ids, rows)
         forward = dec.step
     else:
-        cache = KVCache(model.config, B, P + new, input_ids.device, _cache_dtype(model))
+        cache = KVCache(model.config, B, P + new, input_ids.device, _kv_dtype(model, kv))
         logits = forward_cached(model, input_ids, cache, rows)
 
         def forward(nxt):

@@ -428,3 +428,34 @@ def spec_accept(drafts, cand, n: int, max_new_tokens: int, eos_ids=(), finished:
         if out[-1] in eos_ids:
             return out, True, n + len(out) - 1
     return out, False, -1
+
+
+# ----------------------------------------------------------------------------- fp8 KV cache
+# The format of the fp8 KV cache (csrc/kernels/kv_fp8.hip, decode_attention.hip): OCP e4m3fn codes
+# with one fp32 scale per head vector (one (token, kv head) of K or V). This is the definition; the
+# device quantiser reproduces it bit for bit on bf16 inputs.
+KV_FP8_MAX = 448.0  # the largest finite e4m3fn value (code 126)
+
+
+def kv_fp8_table() -> torch.Tensor:
+    """The 256 fp32 values of the OCP e4m3fn codes (0x7F / 0xFF are NaN)."""
+    return torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float()
+
+
+def kv_fp8_quantize(x):
+    """x [..., D] -> (uint8 codes [..., D], fp32 scale [...]): scale = max|x| / 448 over the last
+    dim (1.0 for an all-zero vector), code = x / scale clamped to +-448 and rounded to nearest-even
+    e4m3fn. The vector's largest element gets code 126, no NaN code is produced for finite x, and
+    |dequant - x| <= max(|x| 2^-4, scale 2^-10) (half an ulp of 3 mantissa bits, or half the
+    subnormal step)."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    scale = torch.where(amax == 0, torch.ones_like(amax), amax / KV_FP8_MAX)
+    y = (xf / scale.unsqueeze(-1)).clamp(-KV_FP8_MAX, KV_FP8_MAX)
+    return y.to(torch.float8_e4m3fn).view(torch.uint8), scale
+
+
+def kv_fp8_dequantize(codes, scale, dtype=torch.float32):
+    """table[code] * scale (fp32 product), rounded to ``dtype``."""
+    table = kv_fp8_table().to(codes.device)
+    return (table[codes.long()] * scale.float().unsqueeze(-1)).to(dtype)

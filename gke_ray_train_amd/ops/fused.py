@@ -309,6 +309,28 @@ def decode_attention_multi(q, k, v, seqlens_k=None, scale=None):
     return torch.cat(out, 1)
 
 
+def decode_attention_fp8(q, kc, vc, k_scale, v_scale, seqlens_k=None, scale=None):
+    """Decode attention over an fp8 KV cache: q [B, T, Hq, D] bf16, T = 1..4 new tokens per row whose
+    keys are the last T valid ones; kc / vc [B, L, Hkv, D] uint8 e4m3fn codes and k_scale / v_scale
+    [B, L, Hkv] fp32, one scale per (key, kv head) (``_ref.kv_fp8_quantize``); ``seqlens_k`` and the
+    token rule as in ``decode_attention_multi``. On the GPU the split-K decode kernel reads the
+    codes as they are (decode_attention.hip, head_dim 128 or 64; anything else is an error). The
+    CPU dequantises and takes the fp32 math path."""
+    B, T, Hq, D = q.shape
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if _gpu(q):
+        C = _native.kernels()
+        if D not in (64, 128):
+            raise ValueError(f"decode_attention_fp8: no gfx950 kernel for head_dim {D} (64 or 128)")
+        return (C.attn_decode_fp8 if D == 128 else C.attn_decode_fp8_d64)(q, kc, vc, k_scale, v_scale, seqlens_k, scale)
+    k = _ref.kv_fp8_dequantize(kc, k_scale, q.dtype)
+    v = _ref.kv_fp8_dequantize(vc, v_scale, q.dtype)
+    lens = seqlens_k.long() if seqlens_k is not None else torch.full((B,), k.shape[1], dtype=torch.long)
+    out = [_ref.attention(q[:, t:t + 1], k, v, causal=False, scale=scale, seqlens_k=lens - (T - 1 - t))
+           for t in range(T)]
+    return torch.cat(out, 1)
+
+
 _warned = set()
 
 

@@ -39,14 +39,15 @@ def _load_base(model_id, device, dtype, seed=0):
 
 def run_inference_comparison(original_model_id, path_to_fine_tuned_model, eval_rows, max_seq_len, results_output_dir,
                              device, max_new_generation_tokens=150, tokenizer=None, batch_size=1,
-                             prompt_lookup_num_tokens=None, max_matching_ngram_size=2):
+                             prompt_lookup_num_tokens=None, max_matching_ngram_size=2, kv_cache_dtype=None):
     """Greedy generation of the original vs fine-tuned model on 'window functions' samples.
 
     ``batch_size`` = k sends the prompts of k samples through one ``generate`` call per model,
     left-padded with an attention mask; 1 (the default) is one call per sample, as the reference.
     ``prompt_lookup_num_tokens`` = K (1-3, batch_size 1 only) turns on prompt-lookup speculative
     decoding in ``generate``: the same answers from fewer passes over the weights where the answer
-    copies names out of the schema in the prompt."""
+    copies names out of the schema in the prompt. ``kv_cache_dtype="fp8"`` keeps the KV cache of
+    ``generate`` as fp8 codes, about half the bf16 cache's bytes (None: the model's dtype)."""
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")
     from gke_ray_train_amd.data.tokenizer import ByteTokenizer
@@ -69,6 +70,8 @@ def run_inference_comparison(original_model_id, path_to_fine_tuned_model, eval_r
         prompts = [format_chat_sample(s, tok, with_answer=False)["text"] for s in chunk]
         rows = [tok.encode(p)[:budget] for p in prompts]
         kw = {}
+        if kv_cache_dtype is not None:
+            kw["kv_cache_dtype"] = kv_cache_dtype
         if prompt_lookup_num_tokens:
             kw.update(prompt_lookup_num_tokens=prompt_lookup_num_tokens,
                       max_matching_ngram_size=max_matching_ngram_size)

@@ -15,7 +15,12 @@ token picked on the device inside the captured step against the host loop (``sam
 prompt_lookup_num_tokens=K)``, device loop) against the plain device loop (``spec_main``).
 
 ``DECODE_ATTN=1`` times the multi-token decode attention kernel alone against T launches of the
-one-token kernel (``attn_main``)."""
+one-token kernel (``attn_main``).
+
+``DECODE_KV=fp8`` times the fp8 KV cache (``generate(..., kv_cache_dtype="fp8")``) against the bf16
+cache, device loop, ``DECODE_B`` sequences with a prompt of ``DECODE_PROMPT`` (512) tokens
+(``kv_main``); with ``DECODE_ATTN=1`` it times the decode attention kernel alone over an fp8 and a
+bf16 cache instead (``kv_attn_main``)."""
 import json
 import os
 import sys
@@ -198,8 +203,100 @@ def attn_main():
                                   "multi_us": round(us_m, 2), "T_single_launches_us": round(us_1, 2)}), flush=True)
 
 
+def kv_main():
+    """``DECODE_KV=fp8``: greedy, ``DECODE_B`` sequences, prompt ``DECODE_PROMPT`` (512), ``DECODE_NEW``
+    (128) tokens, HIP-graph decoder with the device loop; the bf16-cache and the fp8-cache arm
+    alternate ``DECODE_ROUNDS`` (3) times in this one process. The replays are timed on their own
+    with events (prefill, first token and the capturing replay come before the first event), so
+    ``ms_per_step`` is the captured step and nothing else. ``cache_bytes`` is ``KVCache.nbytes()``."""
+    from gke_ray_train_amd.models import generation as G
+    if os.environ["DECODE_KV"] != "fp8":
+        sys.exit("DECODE_KV: only fp8")
+    new = int(os.environ.get("DECODE_NEW", "128"))
+    P = int(os.environ.get("DECODE_PROMPT", "512"))
+    B = int(B_ENV)
+    net = build_llama(model, device="cuda", dtype=torch.bfloat16, seed=0).eval()
+    ids = torch.randint(0, net.config.vocab_size, (B, P), device="cuda")
+    for rnd in range(int(os.environ.get("DECODE_ROUNDS", "3"))):
+        for kv in (None, "fp8"):
+            dec = G.GraphDecoder(net, B, P + new, sampler=G.SamplerConfig(max_new_tokens=new), kv_cache_dtype=kv)
+            dec.first_token(dec.prefill(ids))
+            dec.advance()  # captures the step
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(new - 2):
+                dec.advance()
+            b.record()
+            torch.cuda.synchronize()
+            step = a.elapsed_time(b) / (new - 2)  # ms per replay
+            print(json.dumps({"model": model, "kv_cache": kv or "bf16", "batch": B, "prompt": P, "round": rnd,
+                              "new_tokens": dec.n_emitted, "cache_bytes": dec.cache.nbytes(),
+                              "norm_fused_step": dec.norm_ws is not None, "ms_per_step": round(step, 3),
+                              "decode_tokens_per_s": round(B / step * 1e3, 1)}), flush=True)
+            del dec
+            torch.cuda.empty_cache()
+
+
+def kv_attn_main():
+    """``DECODE_ATTN=1 DECODE_KV=fp8``: ``attn_decode`` (bf16 cache) against ``attn_decode_fp8``, batch 8,
+    32 query / 8 kv heads, head_dim 128 and 64, 600 / 4,096 / 16,384 valid keys (a cache 64 slots
+    longer), T = 1 and 4. Back-to-back launches timed with events, the arms alternating
+    ``DECODE_ROUNDS`` (3) times; ``gbps`` counts the K + V (+ scale) bytes of the valid keys. Each arm
+    rotates over enough copies of its cache that a launch finds none of its K / V in the 256 MiB
+    last-level cache (``DECODE_ROTATE_MB``, default 1024, of cache bytes per arm; 0: one buffer,
+    the cache-warm figure), as the layers of a model do."""
+    from gke_ray_train_amd import _native
+    from gke_ray_train_amd.ops import _ref
+    C = _native.kernels()
+    B, hq, hkv = 8, 32, 8
+
+    rotate = int(os.environ.get("DECODE_ROTATE_MB", "1024")) << 20
+
+    def timed(fn, bufs, iters):
+        for i in range(10):
+            fn(*bufs[i % len(bufs)])
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for i in range(iters):
+            fn(*bufs[i % len(bufs)])
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / iters * 1e3
+
+    for D in (128, 64):
+        bf = {1: C.attn_decode if D == 128 else C.attn_decode_d64,
+              4: C.attn_decode_multi if D == 128 else C.attn_decode_multi_d64}
+        f8 = C.attn_decode_fp8 if D == 128 else C.attn_decode_fp8_d64
+        for n in (600, 4096, 16384):
+            L = n + 64
+            k = torch.randn(B, L, hkv, D, device="cuda", dtype=torch.bfloat16)
+            v = torch.randn(B, L, hkv, D, device="cuda", dtype=torch.bfloat16)
+            (kc, ks), (vc, vs) = [[t.cuda() for t in _ref.kv_fp8_quantize(x.cpu())] for x in (k, v)]
+            sl = torch.full((B,), n, device="cuda", dtype=torch.int32)
+            bytes_bf, bytes_f8 = 2 * B * n * hkv * D * 2, 2 * B * n * hkv * (D + 4)
+            bufs_b = [(k, v)] + [(k.clone(), v.clone()) for _ in range(-(-rotate // bytes_bf) - 1)]
+            bufs_f = [(kc, vc, ks, vs)] + [tuple(t.clone() for t in (kc, vc, ks, vs))
+                                           for _ in range(-(-rotate // bytes_f8) - 1)]
+            iters = 200 if n <= 4096 else 50
+            for T in (1, 4):
+                q = torch.randn(B, T, hq, D, device="cuda", dtype=torch.bfloat16)
+                for rnd in range(int(os.environ.get("DECODE_ROUNDS", "3"))):
+                    us_b = timed(lambda k_, v_: bf[T](q, k_, v_, sl, D ** -0.5), bufs_b, iters)
+                    us_f = timed(lambda *c: f8(q, *c, sl, D ** -0.5), bufs_f, iters)
+                    print(json.dumps({"kernel": "attn_decode_fp8", "head_dim": D, "keys": n, "T": T, "round": rnd,
+                                      "buffers": [len(bufs_b), len(bufs_f)],
+                                      "bf16_us": round(us_b, 2), "fp8_us": round(us_f, 2),
+                                      "bf16_gbps": round(bytes_bf / us_b / 1e3, 1),
+                                      "fp8_gbps": round(bytes_f8 / us_f / 1e3, 1),
+                                      "byte_ratio": round(bytes_f8 / bytes_bf, 3),
+                                      "time_ratio": round(us_f / us_b, 3)}), flush=True)
+
+
 if QUANT:
     nf4_main()
+    sys.exit(0)
+if "DECODE_KV" in os.environ:
+    kv_attn_main() if "DECODE_ATTN" in os.environ else kv_main()
     sys.exit(0)
 if "DECODE_SPEC" in os.environ:
     spec_main()
