@@ -204,7 +204,10 @@ Tensor swiglu_bwd(const Tensor& gu, const Tensor& dout) {
   check_contig(dout, "dout");
   c10::OptionalDeviceGuard g(gu.device());
   const int64_t two_f = gu.size(-1), rows = gu.numel() / two_f, f = two_f / 2;
-  TORCH_CHECK(dout.numel() == rows * f, "dout shape mismatch");
+  check_vec(gu, f, "gu");
+  TORCH_CHECK(dout.numel() == rows * f && dout.scalar_type() == gu.scalar_type() && dout.device() == gu.device(),
+              "dout shape / dtype / device mismatch");
+  check_vec(dout, f, "dout");
   auto dgu = at::empty_like(gu);
   grt::swiglu_bwd(dtype_of(gu), gu.data_ptr(), dout.data_ptr(), dgu.data_ptr(), rows, (int)f, cur_stream(gu));
   return dgu;
@@ -284,6 +287,7 @@ std::vector<Tensor> rope_fwd(const Tensor& qkv, const Tensor& cos, const Tensor&
   check_rope(cos, sin, pos, T, S, D);
   auto q = at::empty({T, hq, D}, qkv.options());
   auto k = at::empty({T, hkv, D}, qkv.options());
+  if (T == 0) return {q, k};
   grt::rope_fwd(dtype_of(qkv), qkv.data_ptr(), ld, q.data_ptr(), k.data_ptr(), cos.data_ptr<float>(),
                 sin.data_ptr<float>(), pos.has_value() ? pos->data_ptr<int32_t>() : nullptr, T, (int)S,
                 (int)hq, (int)hkv, (int)D, cur_stream(qkv));
@@ -390,11 +394,17 @@ void rope_bwd(const Tensor& dq, const Tensor& dk, Tensor& dqkv, const Tensor& co
               const optional<Tensor>& pos, int64_t hq, int64_t hkv, int64_t D, int64_t S) {
   check_contig(dq, "dq");
   check_contig(dk, "dk");
-  TORCH_CHECK(dqkv.dim() == 2 && dqkv.stride(1) == 1, "dqkv must be [T, ld]");
+  check_cuda(dqkv, "dqkv");
+  TORCH_CHECK(dqkv.dim() == 2 && dqkv.stride(1) == 1, "dqkv must be [T, ld] with unit column stride");
+  TORCH_CHECK(dk.scalar_type() == dq.scalar_type() && dqkv.scalar_type() == dq.scalar_type() &&
+              dk.device() == dq.device() && dqkv.device() == dq.device(), "dq / dk / dqkv must share dtype and device");
   c10::OptionalDeviceGuard g(dq.device());
   const int64_t T = dqkv.size(0), ld = dqkv.stride(0);
   TORCH_CHECK(dq.numel() == T * hq * D && dk.numel() == T * hkv * D, "dq/dk shape");
+  TORCH_CHECK(dqkv.size(1) >= (hq + hkv) * D, "dqkv too narrow");
+  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(dqkv.data_ptr()) % 16 == 0, "dqkv alignment");
   check_rope(cos, sin, pos, T, S, D);
+  if (T == 0) return;
   grt::rope_bwd(dtype_of(dq), dq.data_ptr(), dk.data_ptr(), dqkv.data_ptr(), ld, cos.data_ptr<float>(),
                 sin.data_ptr<float>(), pos.has_value() ? pos->data_ptr<int32_t>() : nullptr, T, (int)S,
                 (int)hq, (int)hkv, (int)D, cur_stream(dq));
@@ -689,7 +699,8 @@ std::vector<Tensor> ce_fwd(const Tensor& logits, const Tensor& labels, int64_t i
   check_cuda(logits, "logits");
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [N, V] row-major");
   check_contig(labels, "labels");
-  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.numel() == logits.size(0), "labels must be int64 [N]");
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.numel() == logits.size(0) &&
+              labels.device() == logits.device(), "labels must be int64 [N] on the logits' device");
   c10::OptionalDeviceGuard g(logits.device());
   const int64_t N = logits.size(0);
   auto loss = at::empty({N}, logits.options().dtype(at::kFloat));
@@ -703,8 +714,15 @@ Tensor ce_bwd(const Tensor& logits, const Tensor& labels, const Tensor& lse, con
               int64_t ignore_index, bool inplace) {
   check_cuda(logits, "logits");
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [N, V] row-major");
+  check_contig(labels, "labels");
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.numel() == logits.size(0) &&
+              labels.device() == logits.device(), "labels must be int64 [N] on the logits' device");
+  check_contig(lse, "lse");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == logits.size(0) && lse.device() == logits.device(),
+              "lse fp32 [N] on the logits' device");
   check_contig(gscale, "gscale");
-  TORCH_CHECK(gscale.scalar_type() == at::kFloat && gscale.numel() == logits.size(0), "gscale fp32 [N]");
+  TORCH_CHECK(gscale.scalar_type() == at::kFloat && gscale.numel() == logits.size(0) &&
+              gscale.device() == logits.device(), "gscale fp32 [N] on the logits' device");
   c10::OptionalDeviceGuard g(logits.device());
   Tensor d = inplace ? logits : at::empty_like(logits, at::MemoryFormat::Contiguous);
   grt::cross_entropy_bwd(dtype_of(logits), logits.data_ptr(), logits.stride(0), labels.data_ptr<int64_t>(),
@@ -1709,6 +1727,7 @@ Tensor embedding_fwd(const Tensor& ids, const Tensor& w) {
   TORCH_CHECK(d % 8 == 0, "embedding: row width must be a multiple of 8");
   c10::OptionalDeviceGuard g(w.device());
   auto out = at::empty({ids.numel(), d}, w.options());
+  if (ids.numel() == 0) return out;
   grt::embedding_fwd(dtype_of(w), ids.data_ptr<int64_t>(), w.data_ptr(), out.data_ptr(), ids.numel(), (int)d,
                      w.size(0), cur_stream(w));
   return out;
@@ -1717,12 +1736,19 @@ Tensor embedding_fwd(const Tensor& ids, const Tensor& w) {
 void embedding_bwd(const Tensor& dy, const Tensor& ids, const Tensor& dw, bool accumulate) {
   check_contig(dy, "dy");
   check_contig(dw, "dw");
+  check_contig(ids, "ids");
   TORCH_CHECK(ids.scalar_type() == at::kLong, "embedding_bwd: int64 ids");
   TORCH_CHECK(dy.dim() == 2 && dw.dim() == 2 && dy.size(1) == dw.size(1) && dy.size(0) == ids.numel(),
               "embedding_bwd: shapes");
+  TORCH_CHECK(dy.size(1) % 8 == 0, "embedding_bwd: row width must be a multiple of 8");
   TORCH_CHECK(dy.scalar_type() == dw.scalar_type(), "embedding_bwd: dtype");
+  TORCH_CHECK(ids.device() == dy.device() && dw.device() == dy.device(), "embedding_bwd: ids, dy and dw on one device");
   c10::OptionalDeviceGuard g(dy.device());
   const int64_t V = dw.size(0);
+  if (ids.numel() == 0) {  // no token: every row is unhit
+    if (!accumulate) dw.zero_();
+    return;
+  }
   auto flat = ids.reshape({-1});
   auto sorted = flat.sort();
   auto vals = std::get<0>(sorted);

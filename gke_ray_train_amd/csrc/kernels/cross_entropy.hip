@@ -36,6 +36,7 @@ __global__ __launch_bounds__(kNT) void ce_fwd_kernel(const T* __restrict__ logit
 #pragma unroll
     for (int k = 1; k < VE; ++k) mx = fmaxf(mx, a[k]);
     const float mn = fmaxf(m, mx);
+    if (mn == -INFINITY) continue;  // only -inf logits so far: they add nothing (-inf - -inf is NaN)
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < VE; ++k) acc += __expf(a[k] - mn);
@@ -45,6 +46,7 @@ __global__ __launch_bounds__(kNT) void ce_fwd_kernel(const T* __restrict__ logit
   for (int j = nvec * VE + threadIdx.x; j < V; j += kNT) {
     const float a = to_f(x[j]);
     const float mn = fmaxf(m, a);
+    if (mn == -INFINITY) continue;  // as above
     s = s * __expf(m - mn) + __expf(a - mn);
     m = mn;
   }

@@ -240,6 +240,10 @@ def attention(q, k, v, causal=True, scale=None, seqlens_k=None, dropout_p=0.0, s
 
 
 def cross_entropy(logits, labels, ignore_index=-100):
+    """torch's mean cross-entropy, except that a batch with every row ignored gives 0 (and zero
+    gradients) like the GPU path's clamp_min(1) denominator, where torch's mean is 0 / 0 = NaN."""
+    if not bool((labels != ignore_index).any()):
+        return F.cross_entropy(logits.float(), labels, ignore_index=ignore_index, reduction="sum")
     return F.cross_entropy(logits.float(), labels, ignore_index=ignore_index)
 
 

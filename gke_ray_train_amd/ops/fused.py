@@ -519,12 +519,18 @@ def rope_attention(qkv, cos, sin, B, S, hq, hkv, D, causal=True, scale=None, var
 
 
 # ----------------------------------------------------------------------------- cross entropy
+def _ce_counted(labels, ignore_index, V):
+    """The rows the kernels count (cross_entropy.hip): label not ignore_index and inside [0, V). Any
+    other row gets zero loss and zero gradient there, so it must not enter a denominator either."""
+    return (labels != ignore_index) & (labels >= 0) & (labels < V)
+
+
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ignore_index, inplace):
         C = _native.kernels()
         loss_rows, lse = C.ce_fwd(logits, labels, ignore_index)
-        nvalid = (labels != ignore_index).sum().clamp_min(1).float()
+        nvalid = _ce_counted(labels, ignore_index, logits.shape[1]).sum().clamp_min(1).float()
         ctx.save_for_backward(logits, labels, lse, nvalid)
         ctx.ignore_index, ctx.inplace = ignore_index, inplace
         return loss_rows.sum() / nvalid
@@ -559,10 +565,10 @@ class _LMHeadCE(torch.autograd.Function):
         logits = torch.nn.functional.linear(hidden, weight, bias)
         loss_rows, lse = C.ce_fwd(logits, labels, ignore_index)
         if row_weights is None:
-            scale = (labels != ignore_index).sum().clamp_min(1).float().reciprocal()
+            scale = _ce_counted(labels, ignore_index, logits.shape[1]).sum().clamp_min(1).float().reciprocal()
             loss = loss_rows.sum() * scale
         else:
-            scale = row_weights * (labels != ignore_index)
+            scale = row_weights * _ce_counted(labels, ignore_index, logits.shape[1])
             loss = (loss_rows.float() * scale).sum()
         ctx.save_for_backward(hidden, weight, logits, labels, lse, scale)
         ctx.wt_ev = transpose_for_backward(weight) if ctx.needs_input_grad[0] else None

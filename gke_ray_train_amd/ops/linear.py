@@ -348,10 +348,11 @@ class _Embedding(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ids, w):
         from .. import _native
-        ctx.save_for_backward(ids)
+        flat = ids.reshape(-1).contiguous()  # what both bindings require
+        ctx.save_for_backward(flat)
         ctx.wshape = w.shape
         ctx.w = w
-        return _native.kernels().embedding_fwd(ids.reshape(-1).contiguous(), w).view(*ids.shape, w.shape[1])
+        return _native.kernels().embedding_fwd(flat, w).view(*ids.shape, w.shape[1])
 
     @staticmethod
     def backward(ctx, dy):

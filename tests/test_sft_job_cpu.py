@@ -148,6 +148,29 @@ def test_lm_head_row_weights_cpu():
     assert h.grad is not None and torch.isfinite(h.grad).all()
 
 
+def test_cross_entropy_all_rows_ignored_cpu():
+    """The CPU path gives what the GPU path gives for a batch with no counted row: loss 0 and zero
+    gradients (torch's mean would be 0 / 0 = NaN); any other batch keeps torch's mean."""
+    import torch
+    import torch.nn.functional as F
+    from gke_ray_train_amd import ops
+    torch.manual_seed(0)
+    for ignore_index in (-100, 0):
+        x = torch.randn(6, 11, requires_grad=True)
+        lab = torch.full((6,), ignore_index)
+        loss = ops.cross_entropy(x, lab, ignore_index)
+        loss.backward()
+        assert loss.item() == 0.0 and bool((x.grad == 0).all())
+        h = torch.randn(6, 16, requires_grad=True)
+        w = torch.randn(11, 16, requires_grad=True)
+        loss = ops.lm_head_cross_entropy(h, w, lab, ignore_index=ignore_index)
+        loss.backward()
+        assert loss.item() == 0.0 and bool((h.grad == 0).all()) and bool((w.grad == 0).all())
+        lab = torch.tensor([1, ignore_index, 10, 3, ignore_index, 5])
+        x = torch.randn(6, 11)
+        assert torch.equal(ops.cross_entropy(x, lab, ignore_index), F.cross_entropy(x, lab, ignore_index=ignore_index))
+
+
 def test_padding_free_pack_layout(tmp_path):
     """Packed step: real tokens only (plus one masked filler segment up to the pad multiple), per-token
     weights summing to 1 over the valid next-token targets, sequence lengths for ops.Varlen."""
