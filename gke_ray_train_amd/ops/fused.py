@@ -13,7 +13,7 @@ import torch
 
 from .. import _native
 from . import _ref
-from .linear import input_grad, transpose_for_backward, wgrad
+from .linear import grad_slot, input_grad, transpose_for_backward, wgrad, wgrad_into_slot
 
 
 def _gpu(t: torch.Tensor) -> bool:
@@ -56,13 +56,12 @@ def _norm_bwd_into_slot(w, run):
     """RMSNorm backward whose weight gradient the kernel writes in the parameter dtype straight into
     the data-parallel gradient slot (``w._grt_slot``, parallel/ddp.py / fsdp.py) -> (dx, None);
     without a slot -> (dx, dw)."""
-    slot = getattr(w, "_grt_slot", None) if _NORM_DIRECT_GRAD else None
-    if slot is None or not w.requires_grad or slot.view.dtype != w.dtype:
+    slot = grad_slot(w, match_dtype=True) if _NORM_DIRECT_GRAD else None
+    if slot is None:
         dx, dw = run(None, False)
         return dx, dw.to(w.dtype)
     res = []
-    slot.write(lambda v: res.append(run(v, False)[0]), lambda v: res.append(run(v, True)[0]))
-    slot.notify(w)
+    slot.write(w, lambda v, acc: res.append(run(v, acc)[0]))
     return res[0], None
 
 
@@ -586,12 +585,7 @@ class _LMHeadCE(torch.autograd.Function):
             dh = input_grad(dlogits, weight, ctx.wt_ev)
             ctx.wt_ev = None
         if ctx.needs_input_grad[1]:
-            slot = getattr(weight, "_grt_slot", None)
-            if slot is not None:   # GEMM writes dW straight into the DDP bucket (ops/linear.py)
-                slot.write(lambda v: wgrad(dlogits, hidden, v, False), lambda v: wgrad(dlogits, hidden, v, True))
-                slot.notify(weight)
-            else:
-                dw = wgrad(dlogits, hidden)
+            dw = wgrad_into_slot(weight, lambda v, acc: wgrad(dlogits, hidden, v, acc))
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = dlogits.sum(0)
         return dh, dw, db, None, None, None

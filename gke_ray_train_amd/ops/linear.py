@@ -26,6 +26,11 @@ class GradSlot:
     ``direct`` marks that the backward GEMM wrote this step's contribution itself. Torch still
     fires the parameter's post-accumulate-grad hook for that input (with no gradient), so the
     engines' hooks consume the flag and skip that event instead of counting the parameter twice.
+
+    Writers: ``write(param, fn)`` for one slot; a launch that fills several slots reads each
+    slot's ``accumulate``, launches once, then calls ``wrote(param)`` on each. The engines'
+    post-accumulate-grad hooks ``fold`` autograd's gradient in. ``fresh`` is set again only by the
+    engines' per-step resets.
     """
     __slots__ = ("view", "fresh", "notify", "direct")
 
@@ -35,19 +40,52 @@ class GradSlot:
         self.notify = notify
         self.direct = False
 
-    def write(self, fn_out, fn_acc):
-        if self.fresh:
-            fn_out(self.view)
-            self.fresh = False
-        else:
-            fn_acc(self.view)
+    @property
+    def accumulate(self) -> bool:
+        """beta / the accumulate flag of the next write: False on a step's first contribution."""
+        return not self.fresh
+
+    def write(self, param, fn):
+        fn(self.view, self.accumulate)
+        self.wrote(param)
+
+    def wrote(self, param):
+        self.fresh = False
         self.direct = True
+        self.notify(param)
+
+    def fold(self, grad):
+        """AccumulateGrad side: copy (fresh) or add ``grad`` into the view, unless it is the view."""
+        if grad is not None and grad.data_ptr() != self.view.data_ptr():
+            with torch.no_grad():
+                self.view.copy_(grad) if self.fresh else self.view.add_(grad)
+        self.fresh = False
 
     def consume_direct(self) -> bool:
         if self.direct:
             self.direct = False
             return True
         return False
+
+
+def grad_slot(p, match_dtype: bool = False):
+    """The gradient slot of the trainable parameter ``p`` or None; with ``match_dtype`` only a slot
+    whose view has the parameter's dtype (e.g. not fp32 gradient buffers under bf16 parameters)."""
+    sl = getattr(p, "_grt_slot", None) if p.requires_grad else None
+    if sl is not None and match_dtype and sl.view.dtype != p.dtype:
+        return None
+    return sl
+
+
+def wgrad_into_slot(w, fn):
+    """dW through ``fn(out, accumulate)``: into ``w``'s gradient slot (-> None), else a new tensor."""
+    slot = grad_slot(w)
+    if slot is None:
+        dw = torch.empty_like(w)
+        fn(dw, False)
+        return dw
+    slot.write(w, fn)  # the GEMM writes dW straight into the data-parallel bucket
+    return None
 
 
 _WGRAD_NATIVE = os.environ.get("GRT_WGRAD_GEMM", "1") != "0"
@@ -143,17 +181,6 @@ def input_grad(dy2: torch.Tensor, w: torch.Tensor, wt_ev=None) -> torch.Tensor:
 _NATIVE_EMBEDDING = os.environ.get("GRT_NATIVE_EMBEDDING", "0") == "1"
 
 
-# Where the two transposes of the TN weight gradient run (opt-in placements). GRT_WGRAD_XT_FWD=1:
-# the inputs X of a projection are transposed in the FORWARD, right after the kernel that produced
-# them (norm, SwiGLU, attention) while they may still sit in the 256 MB Infinity Cache, and X^T is
-# saved for the backward instead of X; GRT_WGRAD_DYT_FIRST=1: dY^T at the top of the backward,
-# right after its producer. Measured on the headline step (3 interleaved rounds, scripts/gpu_r4_xt.sh,
-# profiles/r4_batch1.md): 298.4-298.7 / 298.3-298.9 ms vs 298.7-298.9 ms with the transposes inside
-# ``wgrad`` — no cache benefit, +2 GiB peak (the attention output is saved twice), so both stay off.
-_WGRAD_XT_FWD = os.environ.get("GRT_WGRAD_XT_FWD", "0") == "1"
-_WGRAD_DYT_FIRST = os.environ.get("GRT_WGRAD_DYT_FIRST", "0") == "1"
-
-
 def _tn_wgrad_ok(t2: torch.Tensor) -> bool:
     """``t2`` ([M, C] token-major) can be an operand of the transposed (TN) weight-gradient path."""
     return (_WGRAD_NATIVE and _WGRAD_TN and t2.is_cuda and t2.dtype == torch.bfloat16 and t2.dim() == 2
@@ -186,13 +213,18 @@ def provided_transposed(t2: torch.Tensor, t: torch.Tensor):
     return None
 
 
+def _mm_into(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, accumulate: bool) -> torch.Tensor:
+    """out (+)= a @ b on the library GEMM: beta = 1 (in-epilogue accumulation) or 0 (out not read)."""
+    if accumulate:
+        out.addmm_(a, b)
+    else:
+        torch.mm(a, b, out=out)
+    return out
+
+
 def wgrad_tn(dyt: torch.Tensor, xt: torch.Tensor, out: torch.Tensor, accumulate: bool) -> torch.Tensor:
     """dW = dY^T X from the already transposed operands ([N, M], [K, M]): the TN library GEMM."""
-    if accumulate:
-        out.addmm_(dyt, xt.t())
-    else:
-        torch.mm(dyt, xt.t(), out=out)
-    return out
+    return _mm_into(dyt, xt.t(), out, accumulate)
 
 
 def wgrad(dy2: torch.Tensor, x2: torch.Tensor, out: torch.Tensor = None, accumulate: bool = False) -> torch.Tensor:
@@ -218,22 +250,11 @@ def wgrad(dy2: torch.Tensor, x2: torch.Tensor, out: torch.Tensor = None, accumul
             # with its offline-tuned solutions (tools/tune_wgrad_tn.py; untuned microbench incl.
             # the transposes, tools/wgrad_transpose_ab.py: qkv 714 -> 617 us, o 242 -> 221, gate_up
             # 1362 -> 1287, LM head 1880 -> 1594; profiles/r2_perf_experiments.md)
-            dyt = torch.empty(N, M, device=dy2.device, dtype=dy2.dtype)
-            xt = torch.empty(K, M, device=x2.device, dtype=x2.dtype)
-            C.transpose_into(dy2, dyt)
-            C.transpose_into(x2, xt)
-            if accumulate:
-                out.addmm_(dyt, xt.t())
-            else:
-                torch.mm(dyt, xt.t(), out=out)
-            return out
+            dyt = transposed(dy2)
+            return _mm_into(dyt, transposed(x2).t(), out, accumulate)
         if C.gemm_wgrad(dy2, x2, out, accumulate):
             return out
-    if accumulate:
-        out.addmm_(dy2.t(), x2)
-    else:
-        torch.mm(dy2.t(), x2, out=out)
-    return out
+    return _mm_into(dy2.t(), x2, out, accumulate)
 
 
 class _DirectGradLinear(torch.autograd.Function):
@@ -243,8 +264,6 @@ class _DirectGradLinear(torch.autograd.Function):
         # X^T written by the producing kernel (ops.fused.swiglu: the down projection's input)
         xt = provided_transposed(x2, x) if ctx.needs_input_grad[1] else None
         ctx.x_t = xt is not None and w.shape[0] % 64 == 0 and _tn_wgrad_ok(x2)
-        if not ctx.x_t and _WGRAD_XT_FWD and ctx.needs_input_grad[1] and w.shape[0] % 64 == 0 and _tn_wgrad_ok(x2):
-            ctx.x_t, xt = True, transposed(x2)
         ctx.save_for_backward(xt if ctx.x_t else x, w)
         ctx.has_b = b is not None
         ctx.wt_ev = transpose_for_backward(w) if ctx.needs_input_grad[0] else None
@@ -256,42 +275,29 @@ class _DirectGradLinear(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1])
         # dY^T written by the producing kernel (ops.fused.swiglu backward: the gate / up gradient)
         dyt = provided_transposed(dy2, dy) if ctx.needs_input_grad[1] else None
-        if dyt is not None and not ctx.x_t:  # X was saved untransposed: its transpose now
+        xt = x if ctx.x_t else None
+        if dyt is not None and xt is None:  # X was saved untransposed: its transpose now
             x2 = x.reshape(-1, x.shape[-1])
             if _tn_wgrad_ok(x2) and w.shape[0] % 64 == 0:
-                x = transposed(x2)
-                ctx.x_t = True
+                xt = transposed(x2)
             else:  # X cannot take the TN path (dtype / shape / layout): plain weight gradient
                 dyt = None
-        if ctx.x_t and dyt is None:  # X^T saved by the forward: dY^T now, while dY is fresh from its producer
-            if not dy2.is_contiguous():
-                dy2 = dy2.contiguous()
-            dyt = transposed(dy2) if _WGRAD_DYT_FIRST else None
-        dx = None
+        if xt is not None and dyt is None:  # X^T saved by the forward: dY^T below, after the dX GEMM
+            dy2 = dy2.contiguous()
+        dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = input_grad(dy, w, ctx.wt_ev)
             ctx.wt_ev = None
-        dw = db = None
-        if ctx.x_t:
-            xt = x
-            if dyt is None:
-                dyt = transposed(dy2)
-            fn = lambda v, acc: wgrad_tn(dyt, xt, v, acc)  # noqa: E731
-        else:
-            x2 = x.reshape(-1, x.shape[-1])
-            fn = lambda v, acc: wgrad(dy2, x2, v, acc)  # noqa: E731
         if ctx.needs_input_grad[1]:
-            slot = getattr(w, "_grt_slot", None)
-            if slot is not None:
-                slot.write(lambda v: fn(v, False), lambda v: fn(v, True))
-                slot.notify(w)
+            if xt is not None:
+                if dyt is None:
+                    dyt = transposed(dy2)
+                dw = wgrad_into_slot(w, lambda v, acc: wgrad_tn(dyt, xt, v, acc))
             else:
-                dw = torch.empty_like(w)
-                fn(dw, False)
-        if ctx.has_b:
-            b_needs = ctx.needs_input_grad[2]
-            if b_needs:
-                db = dy2.sum(0)
+                x2 = x.reshape(-1, x.shape[-1])
+                dw = wgrad_into_slot(w, lambda v, acc: wgrad(dy2, x2, v, acc))
+        if ctx.has_b and ctx.needs_input_grad[2]:
+            db = dy2.sum(0)
         return dx, dw, db
 
 
@@ -311,7 +317,7 @@ def _gemv_rows_ok(rows: int, K: int) -> bool:
 
 
 def linear(x, weight, bias=None):
-    if weight.requires_grad and getattr(weight, "_grt_slot", None) is not None and torch.is_grad_enabled():
+    if grad_slot(weight) is not None and torch.is_grad_enabled():
         return _DirectGradLinear.apply(x, weight, bias)
     K = weight.shape[-1]
     if (_GEMV and x.is_cuda and not torch.is_grad_enabled() and x.dtype == torch.bfloat16
@@ -360,11 +366,9 @@ class _Embedding(torch.autograd.Function):
         (ids,) = ctx.saved_tensors
         C = _native.kernels()
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-        w = ctx.w
-        slot = getattr(w, "_grt_slot", None)
+        slot = grad_slot(ctx.w)
         if slot is not None:  # write dW straight into the data-parallel gradient buffer
-            slot.write(lambda v: C.embedding_bwd(dy2, ids, v, False), lambda v: C.embedding_bwd(dy2, ids, v, True))
-            slot.notify(w)
+            slot.write(ctx.w, lambda v, acc: C.embedding_bwd(dy2, ids, v, acc))
             return None, None
         dw = torch.empty(ctx.wshape, device=dy.device, dtype=dy.dtype)
         C.embedding_bwd(dy2, ids, dw, False)

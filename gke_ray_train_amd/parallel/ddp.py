@@ -356,15 +356,8 @@ class DistributedDataParallel(nn.Module):
             sl = self._slots[p]
             if sl.consume_direct():  # the GEMM already wrote and announced this gradient
                 return
-            view = sl.view
-            if p.grad is not view and p.grad.data_ptr() != view.data_ptr():
-                with torch.no_grad():
-                    if sl.fresh:
-                        view.copy_(p.grad)
-                    else:
-                        view.add_(p.grad)
-                p.grad = view
-            sl.fresh = False
+            sl.fold(p.grad)
+            p.grad = sl.view
             self._mark_ready(g, b, p)
         return hook
 

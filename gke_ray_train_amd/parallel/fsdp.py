@@ -491,17 +491,11 @@ class FullyShardedDataParallel(nn.Module):
         sl = u.slots[id(p)]
         if sl.consume_direct():  # the GEMM already wrote and announced this gradient
             return
-        if p.grad is not None and p.grad.data_ptr() != sl.view.data_ptr():
-            with torch.no_grad():
-                sl.view.copy_(p.grad) if sl.fresh else sl.view.add_(p.grad)
-        sl.fresh = False
-        p.grad = None
+        sl.fold(p.grad)
         self._param_ready(p)
 
     def _param_ready(self, p):
         u = p._grt_unit
-        sl = u.slots[id(p)]
-        sl.fresh = False
         p.grad = None
         u.ready += 1
         if u.ready == len(u.params):

@@ -41,7 +41,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _native, ops
-from ..ops.linear import input_grad
+from ..ops.linear import grad_slot, input_grad
 from ..ops.optim import param_generation
 from .quant import NF4Linear
 
@@ -160,10 +160,38 @@ def _packed(ts):
 
 
 def _slot_of(p):
-    sl = getattr(p, "_grt_slot", None) if _LORA_DIRECT_GRAD and p.requires_grad else None
-    if sl is not None and sl.view.dtype != p.dtype:  # e.g. fp32 gradient buffers under bf16 adapters
+    return grad_slot(p, match_dtype=True) if _LORA_DIRECT_GRAD else None
+
+
+def _lora_dB(C, b, dyi, hj, alpha, kernels):
+    """dB_i = alpha dY_i^T h_i into B_i's gradient slot (-> None), else a new tensor. ``kernels``:
+    the K-concatenated form (h' already carries the scaling) tries the one-pass kernel first."""
+    def run(v, acc):
+        if not (kernels and _tred_into(C, dyi, hj, v, alpha, acc, False)):
+            v.addmm_(dyi.t(), hj, beta=1.0 if acc else 0.0, alpha=alpha)
+    sl = _slot_of(b)
+    if sl is not None:
+        sl.write(b, run)
         return None
-    return sl
+    if not kernels:
+        return torch.mm(dyi.t(), hj).mul_(alpha)
+    db = torch.empty(dyi.shape[1], hj.shape[1], device=dyi.device, dtype=dyi.dtype)
+    return db if _tred_into(C, dyi, hj, db, alpha, False, False) else torch.mm(dyi.t(), hj)
+
+
+def _lora_dx(ctx, C, base, dy2, g, acat):
+    """dX = dY W + drop'(g A): adapter term first with the base GEMM accumulating onto it, else the
+    base GEMM and one read-modify-write of dX (lora.hip), else GEMM + dropout backward."""
+    dx = _adapter_then_base_dx(ctx, C, base, dy2, g, acat)
+    if dx is None:
+        dx = _base_input_grad(base, dy2)                   # base dX (frozen weight)
+        bf16 = g.dtype == acat.dtype == dx.dtype == torch.bfloat16
+        if not (_LORA_DX and bf16 and C.lora_dx(g, acat.t().contiguous(), dx, ctx.p, ctx.seed, ctx.offset, True)):
+            if ctx.p > 0:
+                C.dropout_bwd_seeded(g @ acat, dx, ctx.p, ctx.seed, ctx.offset, True)
+            else:
+                dx.addmm_(g, acat)
+    return dx
 
 
 class _LoraFn(torch.autograd.Function):
@@ -229,51 +257,11 @@ class _LoraFn(torch.autograd.Function):
         for j, i in enumerate(order):
             off, n = spec[i]
             dyi = dy2[:, off:off + n]
-            hj = h[:, j * r:(j + 1) * r]
             g[:, j * r:(j + 1) * r].addmm_(dyi, Bs[i], beta=0.0, alpha=s)
-            sl = _slot_of(Bs[i])
-            if sl is not None:                               # dB_i = s dY_i^T h_i into the slot
-                sl.write(lambda v: v.addmm_(dyi.t(), hj, beta=0.0, alpha=s), lambda v: v.addmm_(dyi.t(), hj, alpha=s))
-                sl.notify(Bs[i])
-            else:
-                dBs[i] = torch.mm(dyi.t(), hj).mul_(s)
-        dAs: List[Optional[torch.Tensor]] = [None] * k
-        aslots = [_slot_of(As[i]) for i in order]
-        pk = None
-        if all(sl is not None for sl in aslots) and len({sl.fresh for sl in aslots}) == 1:
-            pk = _packed([sl.view for sl in aslots])
-        if pk is not None and pk[0] == list(range(k)):      # slots adjacent in the same order
-            dst = pk[1]
-            if aslots[0].fresh:
-                dst.addmm_(g.t(), xd, beta=0.0)
-            else:
-                dst.addmm_(g.t(), xd)
-            for sl, i in zip(aslots, order):
-                sl.fresh, sl.direct = False, True
-                sl.notify(As[i])
-        else:
-            dacat = g.t() @ xd                               # [r * k, in]
-            for j, i in enumerate(order):
-                rows = dacat[j * r:(j + 1) * r]
-                sl = aslots[j]
-                if sl is not None:
-                    sl.write(lambda v: v.copy_(rows), lambda v: v.add_(rows))
-                    sl.notify(As[i])
-                else:
-                    dAs[i] = rows
+            dBs[i] = _lora_dB(C, Bs[i], dyi, h[:, j * r:(j + 1) * r], s, kernels=False)  # s dY_i^T h_i
+        dAs = _lora_dA(g, xd, As, order, r)
         if ctx.needs_input_grad[0]:
-            dx = _adapter_then_base_dx(ctx, C, ctx.base, dy2, g, acat)
-        if ctx.needs_input_grad[0] and dx is None:
-            dx = _base_input_grad(ctx.base, dy2)           # base dX (frozen weight)
-            # dx += drop'(g A): one read-modify-write of dx (lora.hip), else GEMM + dropout backward
-            bf16 = g.dtype == acat.dtype == dx.dtype == torch.bfloat16 and g.is_cuda
-            if not (_LORA_DX and bf16 and C.lora_dx(g, acat.t().contiguous(), dx, ctx.p, ctx.seed, ctx.offset, True)):
-                if ctx.p > 0:
-                    C.dropout_bwd_seeded(g @ acat, dx, ctx.p, ctx.seed, ctx.offset, True)
-                else:
-                    dx.addmm_(g, acat)
-        if dx is not None:
-            dx = dx.view(ctx.xshape)
+            dx = _lora_dx(ctx, C, ctx.base, dy2, g, acat).view(ctx.xshape)
         return (dx, None, None, None, None, None, None, None, *dAs, *dBs)
 
 
@@ -340,75 +328,50 @@ class _LoraKcatFn(torch.autograd.Function):
             db_done = C.lora_tred_group(
                 [dy2[:, mod._spec[i][0]:mod._spec[i][0] + mod._spec[i][1]] for i in order],
                 [hc[:, j * r:(j + 1) * r] for j in range(len(order))], outs, 1.0,
-                [sl is not None and not sl.fresh for sl in slots])
+                [sl is not None and sl.accumulate for sl in slots])
             if db_done:
                 for sl, o, i in zip(slots, outs, order):
                     if sl is not None:
-                        sl.fresh, sl.direct = False, True
-                        sl.notify(Bs[i])
+                        sl.wrote(Bs[i])
                     else:
                         dBs[i] = o
         for j, i in enumerate(order):
             off, n, _ = mod._spec[i]
             dyi = dy2[:, off:off + n]
-            hj = hc[:, j * r:(j + 1) * r]                    # h' = s h: dB_i = dY_i^T h'_i
             gj = g[:, j * r:(j + 1) * r]
             if not (g_done or (bt is not None and C.lora_g(dyi, bt[j * r:(j + 1) * r, off:off + n], gj, s, False))):
                 gj.addmm_(dyi, Bs[i], beta=0.0, alpha=s)
-            if db_done:
-                continue
-            sl = _slot_of(Bs[i])
-            if sl is not None:
-                sl.write(lambda v: _tred_into(C, dyi, hj, v, 1.0, False, False) or v.addmm_(dyi.t(), hj, beta=0.0),
-                         lambda v: _tred_into(C, dyi, hj, v, 1.0, True, False) or v.addmm_(dyi.t(), hj))
-                sl.notify(Bs[i])
-            else:
-                dBs[i] = torch.empty(n, r, device=dy2.device, dtype=dy2.dtype)
-                if not _tred_into(C, dyi, hj, dBs[i], 1.0, False, False):
-                    dBs[i] = torch.mm(dyi.t(), hj)
+            if not db_done:                                  # h' = s h: dB_i = dY_i^T h'_i
+                dBs[i] = _lora_dB(C, Bs[i], dyi, hc[:, j * r:(j + 1) * r], 1.0, kernels=True)
         dAs = _lora_dA(g, xd, As, order, r, C)
         if ctx.needs_input_grad[0]:
-            dx = _adapter_then_base_dx(ctx, C, mod.base, dy2, g, acat)
-        if ctx.needs_input_grad[0] and dx is None:
-            dx = _base_input_grad(mod.base, dy2)
-            bf16 = g.dtype == acat.dtype == dx.dtype == torch.bfloat16
-            if not (_LORA_DX and bf16 and C.lora_dx(g, acat.t().contiguous(), dx, ctx.p, ctx.seed, ctx.offset, True)):
-                if ctx.p > 0:
-                    C.dropout_bwd_seeded(g @ acat, dx, ctx.p, ctx.seed, ctx.offset, True)
-                else:
-                    dx.addmm_(g, acat)
+            dx = _lora_dx(ctx, C, mod.base, dy2, g, acat)
         return (dx, None, None, None, None, None, *dAs, *dBs)
 
 
 def _lora_dA(g, xd, As, order, r, C=None):
-    """dA_cat = g^T x_d, written into the (adjacent) gradient slots when the engine provides them."""
+    """dA_cat = g^T x_d, written into the (adjacent) gradient slots when the engine provides them;
+    with ``C`` (K-concatenated form) on the one-pass kernel where it applies."""
     k = len(As)
     dAs: List[Optional[torch.Tensor]] = [None] * k
     aslots = [_slot_of(As[i]) for i in order]
     pk = None
-    if all(sl is not None for sl in aslots) and len({sl.fresh for sl in aslots}) == 1:
+    if all(sl is not None for sl in aslots) and len({sl.accumulate for sl in aslots}) == 1:
         pk = _packed([sl.view for sl in aslots])
-    if pk is not None and pk[0] == list(range(k)):
-        dst = pk[1]
-        fresh = aslots[0].fresh
-        if not (C is not None and _tred_into(C, xd, g, dst, 1.0, not fresh, True)):  # dA^T = x_d^T g
-            if fresh:
-                dst.addmm_(g.t(), xd, beta=0.0)
-            else:
-                dst.addmm_(g.t(), xd)
+    if pk is not None and pk[0] == list(range(k)):          # slots adjacent in the same order
+        dst, acc = pk[1], aslots[0].accumulate
+        if not (C is not None and _tred_into(C, xd, g, dst, 1.0, acc, True)):  # dA^T = x_d^T g
+            dst.addmm_(g.t(), xd, beta=1.0 if acc else 0.0)
         for sl, i in zip(aslots, order):
-            sl.fresh, sl.direct = False, True
-            sl.notify(As[i])
+            sl.wrote(As[i])
     else:
-        dacat = torch.empty(g.shape[1], xd.shape[1], device=g.device, dtype=g.dtype)
-        if not (C is not None and _tred_into(C, xd, g, dacat, 1.0, False, True)):
-            dacat = g.t() @ xd
+        dacat = torch.empty(g.shape[1], xd.shape[1], device=g.device, dtype=g.dtype) if C is not None else None
+        if dacat is None or not _tred_into(C, xd, g, dacat, 1.0, False, True):
+            dacat = g.t() @ xd                               # [r * k, in]
         for j, i in enumerate(order):
             rows = dacat[j * r:(j + 1) * r]
-            sl = aslots[j]
-            if sl is not None:
-                sl.write(lambda v: v.copy_(rows), lambda v: v.add_(rows))
-                sl.notify(As[i])
+            if aslots[j] is not None:
+                aslots[j].write(As[i], lambda v, acc: v.add_(rows) if acc else v.copy_(rows))
             else:
                 dAs[i] = rows
     return dAs
@@ -486,48 +449,26 @@ class LoraLinear(nn.Module):
             self._wk[:, K:].zero_()
             self._wk_order = list(order)
             self._wk_key = None
-        bl = [Bs[i].detach() for i in order]
         # Forwards without autograd (``reuse``: evaluation, generation) reuse the tail while B is
         # unchanged: same tensors, same version counters, no framework optimizer step since (the
         # fused kernels write through raw pointers: ops.optim.param_generation). A forward that
         # records a graph always refreshes and drops the key, so a training step never trusts it.
-        key = (tuple(order), tuple((b.data_ptr(), b._version) for b in bl), param_generation())
+        key = (tuple(order), tuple((Bs[i].data_ptr(), Bs[i]._version) for i in order), param_generation())
         if reuse and self._wk_key == key:
             return self._wk
         self._wk_key = key if reuse else None
-        offs = [self._spec[i][0] for i in order]
-        if all(b.is_contiguous() for b in bl):
-            # B^T [R, out] for the adapter-gradient kernel (lora_grad.hip lora_g): block j = B_{order[j]}^T
-            if _LORA_GRAD_KERNELS and r == 64 and self._wk.is_cuda:
-                if self._bt is None:
-                    self._bt = torch.zeros(R, self.out_features, device=self._wk.device, dtype=self._wk.dtype)
-                _native.kernels().lora_refresh(bl, offs, self._wk, self._bt, K, 0)
-            else:
-                _native.kernels().lora_refresh(bl, offs, self._wk, None, K)
-        else:
-            self._bt = None
-            for j, (b, off) in enumerate(zip(bl, offs)):
-                self._wk[off:off + b.shape[0], K + j * r:K + (j + 1) * r].copy_(b)
-        return self._wk
+        return self._refresh_tail(self._wk, order, Bs)
 
-    @torch.no_grad()
-    def _kcat_weight_streamed(self, order, Bs):
-        """W' for an NF4 base without the dequant cache: a fresh [out, in + R] buffer per forward, W
-        dequantised into its head, the B blocks (and the B^T buffer of the adapter-gradient kernel)
-        into the tail. Nothing bf16 of the base outlives the forward's GEMM."""
+    def _refresh_tail(self, wk, order, Bs):
+        """Write the B blocks of the h' column order ``order`` into the tail of ``wk`` (and, for the
+        adapter-gradient kernel lora_grad.hip lora_g, B^T [R, out]: block j = B_{order[j]}^T)."""
         K, r = self.in_features, self.r
-        R = r * len(self.targets)
-        q = self.base.qweight
-        wk = torch.empty(self.out_features, K + R, device=q.device, dtype=torch.bfloat16)
-        self.base.dequantize_into(wk[:, :K])
-        wk[:, K:].zero_()
         bl = [Bs[i].detach() for i in order]
         offs = [self._spec[i][0] for i in order]
         if all(b.is_contiguous() for b in bl):
-            if _LORA_GRAD_KERNELS and r == 64:
-                if self._bt is None or self._wk_order != list(order):
-                    self._bt = torch.zeros(R, self.out_features, device=q.device, dtype=torch.bfloat16)
-                    self._wk_order = list(order)
+            if _LORA_GRAD_KERNELS and r == 64 and wk.is_cuda:
+                if self._bt is None:
+                    self._bt = torch.zeros(r * len(self.targets), self.out_features, device=wk.device, dtype=wk.dtype)
                 _native.kernels().lora_refresh(bl, offs, wk, self._bt, K, 0)
             else:
                 _native.kernels().lora_refresh(bl, offs, wk, None, K)
@@ -536,6 +477,19 @@ class LoraLinear(nn.Module):
             for j, (b, off) in enumerate(zip(bl, offs)):
                 wk[off:off + b.shape[0], K + j * r:K + (j + 1) * r].copy_(b)
         return wk
+
+    @torch.no_grad()
+    def _kcat_weight_streamed(self, order, Bs):
+        """W' for an NF4 base without the dequant cache: a fresh [out, in + R] buffer per forward, W
+        dequantised into its head, the B blocks (and the B^T buffer of the adapter-gradient kernel)
+        into the tail. Nothing bf16 of the base outlives the forward's GEMM."""
+        K, R = self.in_features, self.r * len(self.targets)
+        wk = torch.empty(self.out_features, K + R, device=self.base.qweight.device, dtype=torch.bfloat16)
+        self.base.dequantize_into(wk[:, :K])
+        wk[:, K:].zero_()
+        if self._wk_order != list(order):  # block positions moved: a zeroed B^T buffer
+            self._bt, self._wk_order = None, list(order)
+        return self._refresh_tail(wk, order, Bs)
 
     @torch.no_grad()
     def prepare_frozen_weights(self):

@@ -632,28 +632,37 @@ def test_wgrad_helper_fallback_and_native():
 
 
 def test_direct_grad_linear_transpose_placements_agree(monkeypatch):
-    """X^T taken in the forward (saved instead of X) and dY^T at the top of the backward give the
-    same dX / dW bits as the transposes inside wgrad, into a gradient slot over two accumulating
-    micro-steps, and match the fp32 math."""
+    """X^T handed over by the producer of the input (``x._grt_T``, saved instead of X; dY^T then
+    made in the backward) gives the same dX / dW bits as the op transposing both operands itself
+    inside wgrad, into a gradient slot over two accumulating micro-steps, and matches the fp32 math."""
     from gke_ray_train_amd.ops import linear as L
     g = torch.Generator(device=DEV).manual_seed(11)
     x = torch.randn(2, 192, 512, device=DEV, generator=g).bfloat16()
     w = (torch.randn(384, 512, device=DEV, generator=g) * 0.05).bfloat16()
     dys = [torch.randn(2, 192, 384, device=DEV, generator=g).bfloat16() for _ in range(2)]
+    tn_calls, wgrad_calls = [], []
+    wgrad_tn, wgrad = L.wgrad_tn, L.wgrad
+    monkeypatch.setattr(L, "wgrad_tn", lambda *a: (tn_calls.append(1), wgrad_tn(*a))[1])
+    monkeypatch.setattr(L, "wgrad", lambda *a: (wgrad_calls.append(1), wgrad(*a))[1])
     res = {}
-    for xt_fwd, dyt_first in ((False, False), (True, False), (True, True)):
-        monkeypatch.setattr(L, "_WGRAD_XT_FWD", xt_fwd)
-        monkeypatch.setattr(L, "_WGRAD_DYT_FIRST", dyt_first)
+    for provided in (False, True):
+        del tn_calls[:], wgrad_calls[:]
         wp = torch.nn.Parameter(w.clone())
-        wp._grt_slot = L.GradSlot(torch.empty_like(w), lambda p: None)
+        wp._grt_slot = L.GradSlot(torch.full_like(w, float("nan")), lambda p: None)
         dxs = []
         for dy in dys:
             xi = x.clone().requires_grad_()
+            if provided:
+                xi._grt_T = L.transposed(x.reshape(-1, 512))
             y = L.linear(xi, wp)
+            assert not hasattr(xi, "_grt_T")  # taken by the op
             y.backward(dy)
             dxs.append(xi.grad)
-        res[(xt_fwd, dyt_first)] = (dxs, wp._grt_slot.view.clone())
-    base = res[(False, False)]
+        # both micro-steps: A through wgrad (its own two transposes), B through wgrad_tn on the saved X^T
+        assert (len(tn_calls), len(wgrad_calls)) == ((2, 0) if provided else (0, 2))
+        assert wp._grt_slot.accumulate and wp.grad is None
+        res[provided] = (dxs, wp._grt_slot.view.clone())
+    base = res[False]
     for k, (dxs, dw) in res.items():
         assert all(torch.equal(a, b) for a, b in zip(dxs, base[0])), k
         assert torch.equal(dw, base[1]), k
@@ -1198,12 +1207,14 @@ def test_decode_attention(B, Sk, hq, hkv, pad):
 
 @pytest.mark.parametrize("nf4", [False, True, "stream"])
 @pytest.mark.parametrize("p", [0.0, 0.1])
-@pytest.mark.parametrize("engine", ["none", "ddp"])
+@pytest.mark.parametrize("engine", ["none", "ddp", "ddp_accum"])
 def test_kcat_lora_matches_reference(nf4, p, engine):
     """K-concatenated LoRA (peft/lora.py _LoraKcatFn): the input is the head of a [M, in + R] row
     buffer, h' lands in its tail, y = [x | h'] W'^T and [dX | g] = dY W' are single GEMMs. Same
     y / dX / dA / dB as the fp32 formula (masks regenerated from the seed the op drew).
-    nf4="stream": NF4 base without the dequant cache, W' rebuilt per forward (_kcat_weight_streamed)."""
+    nf4="stream": NF4 base without the dequant cache, W' rebuilt per forward (_kcat_weight_streamed).
+    engine="ddp_accum": two micro-steps (the first under no_sync) accumulate into the gradient slots,
+    so the grouped dB launch and the adjacent-slot dA write run with a true accumulate flag."""
     stream = nf4 == "stream"
     nf4 = bool(nf4)
     from gke_ray_train_amd.ops import _ref
@@ -1232,32 +1243,37 @@ def test_kcat_lora_matches_reference(nf4, p, engine):
     xw[:, 256:] = float("nan")  # the op must write every tail element before the GEMM reads it
     x = xw[:, :256].detach().requires_grad_()
     x._grt_tail = R
-    fwd = mod
-    if engine == "ddp":
+    fwd, eng, reps = mod, None, 1
+    if engine != "none":
         from gke_ray_train_amd.parallel import DistributedDataParallel
-        fwd = DistributedDataParallel(mod)
-        x._grt_tail = R
+        fwd = eng = DistributedDataParallel(mod)
+        reps = 2 if engine == "ddp_accum" else 1
     rng = torch.get_rng_state()
-    y = fwd(x)
-    dy = torch.randn_like(y)
-    (y.float() * dy.float()).sum().backward()
-    if engine == "ddp":
-        fwd.finish_gradient_sync()
+    dy = None
+    for rep in range(reps):
+        with eng.no_sync(rep < reps - 1) if eng is not None else contextlib.nullcontext():
+            xw[:, 256:] = float("nan")
+            y = fwd(x)
+            dy = torch.randn_like(y) if dy is None else dy
+            (y.float() * dy.float()).sum().backward()
+    if eng is not None:
+        eng.finish_gradient_sync()
     torch.set_rng_state(rng)
-    seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
     x2 = x.detach().float().requires_grad_()
     w = (base.dequantize() if nf4 else lin.weight).detach().float()
     A = {n: mod.lora_A[n].detach().float().requires_grad_() for n in names}
     B = {n: mod.lora_B[n].detach().float().requires_grad_() for n in names}
-    if p > 0:
-        keep = _ref.dropout_keep_mask(seed, 0, x2.numel(), p).to(DEV).view_as(x2).float()
-        xd = x2 * keep / (1 - p)
-    else:
-        xd = x2
-    yr = (x2 @ w.t()).clone()
-    for n, off in tg:
-        yr[:, off:off + 256] = yr[:, off:off + 256] + cfg.scaling * (xd @ A[n].t()) @ B[n].t()
-    (yr * dy.float()).sum().backward()
+    for rep in range(reps):  # one seed per micro-step: each forward draws its own
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        if p > 0:
+            keep = _ref.dropout_keep_mask(seed, 0, x2.numel(), p).to(DEV).view_as(x2).float()
+            xd = x2 * keep / (1 - p)
+        else:
+            xd = x2
+        yr = (x2 @ w.t()).clone()
+        for n, off in tg:
+            yr[:, off:off + 256] = yr[:, off:off + 256] + cfg.scaling * (xd @ A[n].t()) @ B[n].t()
+        (yr * dy.float()).sum().backward()
     _close(y, yr, 3e-2, 3e-2, "kcat y")
     _close(x.grad, x2.grad, 3e-2, 3e-2, "kcat dx")
     if stream:
