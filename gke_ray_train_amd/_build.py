@@ -69,6 +69,11 @@ def _check_flags():
     return ["-DGRT_KERNEL_CHECKS=1"] if os.environ.get("GRT_KERNEL_CHECKS", "0") == "1" else []
 
 
+# Extra hipcc flags of single kernel files. gemm_nf4_skinny: no packed fp32 instructions (the
+# compiler would form v_pk_fma_f32 from the per-block absmax FMAs on the accumulator tile).
+KERNEL_FLAGS = {"gemm_nf4_skinny": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def build_kernels(force=False, jobs=8, verbose=False) -> Path:
     tdir, abi = _torch_paths()
     BUILD.mkdir(parents=True, exist_ok=True)
@@ -82,7 +87,8 @@ def build_kernels(force=False, jobs=8, verbose=False) -> Path:
         objs.append(obj)
         if force or _newer(obj, [src, *hdrs]):
             cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast",
-                   "-munsafe-fp-atomics", *_check_flags(), *inc, "-c", str(src), "-o", str(obj)]
+                   "-munsafe-fp-atomics", *KERNEL_FLAGS.get(src.stem, []), *_check_flags(), *inc, "-c", str(src),
+                   "-o", str(obj)]
             tasks.append(cmd)
     pyinc = sysconfig.get_paths()["include"]
     # host sources: the pybind module (ops.cpp) and the host-side runtime pieces it binds (the

@@ -444,6 +444,14 @@ struct Nf4Gemv {
 };
 void gemv_nf4(const Nf4Gemv& f, hipStream_t s);
 
+// ---------------- skinny MFMA GEMM from NF4 codes (gemm_nf4_skinny.hip) ----------------
+// The same operation and arguments for M <= 16 (batched decode), with the weight operand rounded to
+// bf16(level) for the matrix instruction: fp32 sums inside a quant block, times the fp32 absmax,
+// into an fp32 running sum. Additionally h rows, every b[i] and q 16-byte aligned, ldh % 8 == 0.
+using Nf4GemmSkinny = Nf4Gemv;
+constexpr int kNf4SkinnyMaxRows = 16;
+void gemm_nf4_skinny(const Nf4GemmSkinny& f, hipStream_t s);
+
 // ---------------- token sampler (sample.hip) ----------------
 // One token per row of logits [B, V] (bf16 / fp32, row stride ld elements): greedy argmax, or a
 // Gumbel-max draw over the top-k / top-p kept set of logits * inv_t (semantics and the noise

@@ -60,6 +60,7 @@ runs over the dequantised rows. There is no flash-kernel decode path for the fp8
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from dataclasses import dataclass
 from typing import List, Optional, Tuple, Union
@@ -68,6 +69,7 @@ import torch
 
 from .. import _native, ops
 from ..ops import _ref
+from ..peft.quant import decode_step
 
 
 KV_CACHE_DTYPES = (None, "auto", "fp8", "fp8_e4m3")
@@ -348,7 +350,12 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache, attention_mask=None
         raise ValueError(f"KV cache overflow: {pos0} cached + {S} new tokens > max_len {cache.max_len}")
     cos, sin = model.rope(cache.max_len, ids.device)
     h = model.model.embed_tokens(ids).view(B * S, -1)
-    x = _layers(model, h, lambda li, attn, qkv: _eager_attention(attn, qkv, B, S, pos0, cos, sin, cache, li, row_pos))
+    # one token (or one verify chunk) per sequence on top of a cache is a decode step: an NF4 base
+    # may take its B * S rows from the codes (peft/quant.py decode_step); a prefill never is
+    step = decode_step(B * S) if (pos0 > 0 or row_pos is not None) and S <= 4 else contextlib.nullcontext()
+    with step:
+        x = _layers(model, h,
+                    lambda li, attn, qkv: _eager_attention(attn, qkv, B, S, pos0, cos, sin, cache, li, row_pos))
     if all_logits:
         if rows is not None or row_pos is not None:
             raise ValueError("forward_cached: all_logits needs an unpadded, non-ragged cache")
@@ -635,8 +642,9 @@ class GraphDecoder:
             logits = _native.kernels().gemv_fused(h, m.lm_head.weight, self.norm_ws.sumsq, 1, g=fn.weight,
                                                   eps=fn.eps)
         else:
-            logits = m.lm_head(_layers(m, h, lambda li, attn, qkv: _device_attention(
-                attn, qkv, B, T, self.cos, self.sin, self.cache, li, self.pos_b, self.lens)))
+            with decode_step(B * T):  # warm-up and capture; a replay runs what was captured
+                logits = m.lm_head(_layers(m, h, lambda li, attn, qkv: _device_attention(
+                    attn, qkv, B, T, self.cos, self.sin, self.cache, li, self.pos_b, self.lens)))
         return self._step_tail(logits)
 
     def _step_tail(self, logits):

@@ -626,3 +626,15 @@ def nf4_gemv(x, qweight, absmax, N, K, h=None, lora_b=None, lora_off=None, scali
             return _native.kernels().nf4_gemv(x, qweight, absmax, N, K)
         return _native.kernels().nf4_gemv(x, qweight, absmax, N, K, h, list(lora_b), list(lora_off), scaling)
     return _ref.nf4_gemv(x, qweight, absmax, N, K, h, lora_b, lora_off, scaling)
+
+
+def nf4_gemm_skinny(x, qweight, absmax, N, K, h=None, lora_b=None, lora_off=None, scaling=1.0):
+    """``nf4_gemv`` for 1-16 bf16 rows on the skinny MFMA kernel (gemm_nf4_skinny.hip): the decode
+    is paid once per weight whatever the row count. The matrix instruction takes the weight as
+    bf16(level); fp32 sums inside a quant block, times the fp32 absmax, into an fp32 sum. ``h`` rows
+    and every ``lora_b`` 16-byte aligned. Off the GPU: the float reference, which takes any M."""
+    if _gpu(x):
+        if lora_b is None:
+            return _native.kernels().nf4_gemm_skinny(x, qweight, absmax, N, K)
+        return _native.kernels().nf4_gemm_skinny(x, qweight, absmax, N, K, h, list(lora_b), list(lora_off), scaling)
+    return _ref.nf4_gemv(x, qweight, absmax, N, K, h, lora_b, lora_off, scaling)

@@ -530,9 +530,10 @@ class LoraLinear(nn.Module):
         return list(range(len(As))), c[1]
 
     def _decode_forward(self, x) -> Optional[torch.Tensor]:
-        """Decode step on an NF4 base (1-4 rows, no autograd, dropout inactive): h = gemv(x, A_cat),
-        then ONE GEMV from the codes whose epilogue adds every target's s * h_i B_i^T
-        (csrc/kernels/gemv_nf4.hip). None when it does not apply: the caller takes ``_LoraFn``."""
+        """Decode step on an NF4 base (1-4 rows, or a declared ``decode_step`` of 5-16; no autograd,
+        dropout inactive): h = gemv(x, A_cat), then ONE product from the codes whose epilogue adds
+        every target's s * h_i B_i^T (csrc/kernels/gemv_nf4.hip, gemm_nf4_skinny.hip). None when it
+        does not apply: the caller takes ``_LoraFn``."""
         b = self.base
         k = len(self.targets)
         if not (isinstance(b, NF4Linear) and 1 <= k <= 4 and 8 <= self.r <= 64 and self.r % 8 == 0
@@ -550,9 +551,14 @@ class LoraLinear(nn.Module):
         order, acat = self._decode_acat(As)
         if acat.data_ptr() % 16 != 0:
             return None
-        h = _native.kernels().gemv(x2, acat)                   # [rows, r * k], column block j = target order[j]
-        y = ops.nf4_gemv(x2, b.qweight, b._absmax_f32(), self.out_features, self.in_features, h,
-                         [Bs[i].detach() for i in order], [self._spec[i][0] for i in order], self.scaling)
+        rows = x2.shape[0]
+        if rows > 4 and any(t.data_ptr() % 16 != 0 for t in Bs):  # the skinny GEMM's 16-byte loads
+            return None
+        if rows <= 4 or self.in_features % 256 == 0:           # the bf16 GEMV family's domain (gemv_mfma_ok)
+            h = _native.kernels().gemv(x2, acat)               # [rows, r * k], column block j = target order[j]
+        else:
+            h = F.linear(x2, acat)
+        y = b.codes_matmul(x2, h, [Bs[i].detach() for i in order], [self._spec[i][0] for i in order], self.scaling)
         return y.view(*x.shape[:-1], self.out_features)
 
     def direct_grad_params(self) -> List[nn.Parameter]:

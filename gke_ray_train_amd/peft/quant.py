@@ -8,9 +8,14 @@ stored for autograd, so the base model costs ~0.53 bytes/param resident) and run
 GEMM — or, when ``set_dequant_cache`` finds room in HBM (auto for 8B on a 288 GB MI355X), reuse a
 resident dequantised W / W^T (bit-identical; the base is frozen). ``double_quant`` additionally stores the absmax vector as 8-bit codes
 with one fp32 scale per 256 blocks (bitsandbytes' nested quantisation) and expands it on device.
+
+Decode (no autograd) multiplies straight from the codes instead: 1-4 rows on the NF4 GEMV
+(csrc/kernels/gemv_nf4.hip), and the 5-16 rows of a batched decode step, declared by the caller with
+``decode_step(rows)``, on the skinny MFMA GEMM (csrc/kernels/gemm_nf4_skinny.hip).
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -48,6 +53,35 @@ _NF4_GEMV = os.environ.get("GRT_NF4_GEMV", "1") != "0"
 # it takes. GRT_NF4_GEMV_MAX_ROWS lowers the limit.
 NF4_GEMV_KERNEL_ROWS = 4
 NF4_GEMV_MAX_ROWS = min(int(os.environ.get("GRT_NF4_GEMV_MAX_ROWS", NF4_GEMV_KERNEL_ROWS)), NF4_GEMV_KERNEL_ROWS)
+# Batched decode (5-16 rows): the skinny MFMA GEMM from the codes (csrc/kernels/gemm_nf4_skinny.hip).
+# The row count alone does not select it (a prefill chunk or a direct module call of 5-16 rows keeps
+# the dequantising path, bit for bit): the caller declares the forward a decode step of that many
+# rows with ``decode_step`` (models/generation.py does, around every cached one-token / verify step).
+# Row limit: the kernel's own 16. Llama-3.1-8B QLoRA r = 64 graph decode, arms alternating in one
+# process, batch 5 / 8 / 16: 841 / 1265 / 2222 tokens/s from the codes against 577 / 918 / 1794 on the
+# cached bf16 W and 388 / 619 / 1227 dequantising per token (profiles/nf4_decode.md).
+# GRT_NF4_SKINNY_MAX_ROWS lowers the limit; 4 turns the path off.
+NF4_SKINNY_KERNEL_ROWS = 16
+NF4_SKINNY_MAX_ROWS = min(int(os.environ.get("GRT_NF4_SKINNY_MAX_ROWS", NF4_SKINNY_KERNEL_ROWS)),
+                          NF4_SKINNY_KERNEL_ROWS)
+_decode_rows = 0  # rows of the declared decode step, 0 outside one
+
+
+@contextlib.contextmanager
+def decode_step(rows: int):
+    """Declare the forwards inside as one decode step of ``rows`` activation rows (sequences x tokens
+    per sequence). Python-time state: active while a HIP graph of the step is captured, irrelevant
+    when it is replayed."""
+    global _decode_rows
+    prev, _decode_rows = _decode_rows, int(rows)
+    try:
+        yield
+    finally:
+        _decode_rows = prev
+
+
+def _skinny_rows(rows: int) -> bool:
+    return NF4_GEMV_KERNEL_ROWS < rows <= NF4_SKINNY_MAX_ROWS and rows == _decode_rows
 
 
 class _NF4Matmul(torch.autograd.Function):
@@ -131,20 +165,28 @@ class NF4Linear(nn.Module):
         return a
 
     def gemv_input(self, x: torch.Tensor) -> Optional[torch.Tensor]:
-        """``x`` as the [rows, in_features] view the NF4 GEMV takes, or None when the decode kernel
-        does not apply (autograd on, not the GPU / bf16 / blocksize-64 format, in_features % 64,
-        more rows than the limit, unaligned rows): the caller then takes the dequantising path."""
+        """``x`` as the [rows, in_features] view the NF4 kernels take, or None when neither decode
+        kernel applies (autograd on, not the GPU / bf16 / blocksize-64 format, in_features % 64,
+        more rows than the GEMV's limit and no declared ``decode_step`` of exactly that many rows
+        within the skinny GEMM's limit, unaligned rows): the caller then takes the dequantising path."""
         K = self.in_features
         if not (_NF4_GEMV and not torch.is_grad_enabled() and x.is_cuda and self.qweight.is_cuda
                 and self.compute_dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and self.blocksize == 64
                 and K % 64 == 0 and x.shape[-1] == K and x.numel() > 0
-                and x.numel() // K <= NF4_GEMV_MAX_ROWS):
+                and (x.numel() // K <= NF4_GEMV_MAX_ROWS or _skinny_rows(x.numel() // K))):
             return None
         x2 = x.reshape(-1, K)
         if x2.stride(1) != 1 or x2.stride(0) % 8 != 0 or x2.stride(0) < K or x2.data_ptr() % 16 != 0 \
                 or self.qweight.data_ptr() % 16 != 0:
             return None
         return x2
+
+    def codes_matmul(self, x2: torch.Tensor, h=None, lora_b=None, lora_off=None, scaling=1.0) -> torch.Tensor:
+        """y = x2 W^T (+ the LoRA epilogue) from the codes, ``x2`` from ``gemv_input``: 1-4 rows on
+        the GEMV, a declared decode step of 5-16 rows on the skinny MFMA GEMM."""
+        fn = ops.nf4_gemv if x2.shape[0] <= NF4_GEMV_KERNEL_ROWS else ops.nf4_gemm_skinny
+        return fn(x2, self.qweight, self._absmax_f32(), self.out_features, self.in_features, h, lora_b, lora_off,
+                  scaling)
 
     def _dequant(self) -> torch.Tensor:
         n = self.in_features * self.out_features
@@ -220,8 +262,8 @@ class NF4Linear(nn.Module):
         if torch.is_grad_enabled() and x.requires_grad:
             return _NF4Matmul.apply(x, self)
         x2 = self.gemv_input(x)
-        if x2 is not None:  # decode: 1-4 rows straight from the codes
-            y = ops.nf4_gemv(x2, self.qweight, self._absmax_f32(), self.out_features, self.in_features)
+        if x2 is not None:  # decode: straight from the codes
+            y = self.codes_matmul(x2)
             return y.view(*x.shape[:-1], self.out_features)
         return F.linear(x, self.dequantize())
 

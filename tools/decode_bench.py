@@ -4,8 +4,10 @@ reference's inference comparison generates up to MAX_NEW_GENERATION_TOKENS_INFER
 tokens per sample, ray-jobs/fine_tune_config.json:35). One JSON line per mode.
 
 ``DECODE_QUANT=nf4`` (optionally ``DECODE_LORA=<r>``: LoRA on all 7 targets, non-zero lora_B) times
-HIP-graph decode from a 4-bit base instead: the NF4 GEMV (csrc/kernels/gemv_nf4.hip) against the dequantising path it replaces, with the dequant cache
-on and off, the arms alternating ``DECODE_ROUNDS`` (2) times in this one process. ``DECODE_CACHE=0|1``
+HIP-graph decode from a 4-bit base instead: the NF4 GEMV (csrc/kernels/gemv_nf4.hip; batch 5-16: the
+skinny MFMA GEMM, csrc/kernels/gemm_nf4_skinny.hip, switched by its row limit) against the
+dequantising path it replaces, with the dequant cache on and off, the arms alternating
+``DECODE_ROUNDS`` (2) times in this one process. ``DECODE_CACHE=0|1``
 keeps one cache mode (70B: 0); ``DECODE_B`` may be a comma list here.
 
 ``DECODE_SAMPLE=greedy|top_p`` and / or ``DECODE_DEVICE_LOOP=0|1`` times the HIP-graph decoder with the
@@ -65,6 +67,9 @@ def nf4_arms(net, base, quant, ids, B, r, new, caches):
             for kern in (False, True):
                 quant.set_dequant_cache(base, cache)
                 quant._NF4_GEMV = kern
+                if B > quant.NF4_GEMV_KERNEL_ROWS:  # 5-16 sequences: the skinny GEMM's row limit is the switch
+                    quant._NF4_GEMV = True
+                    quant.NF4_SKINNY_MAX_ROWS = quant.NF4_SKINNY_KERNEL_ROWS if kern else quant.NF4_GEMV_KERNEL_ROWS
                 net.generate(ids, max_new_tokens=8, use_graph=True)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()

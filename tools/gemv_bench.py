@@ -8,8 +8,9 @@ per shape.
 
     python tools/gemv_bench.py [--m 1] [--reps 50] [--flush]
 
-``--nf4``: the NF4 GEMV (csrc/kernels/gemv_nf4.hip) on the four quantised projection shapes instead,
-plain and with the r = 64 LoRA epilogue on every sub-projection, as effective TB/s of code bytes
+``--nf4``: the NF4 GEMV (csrc/kernels/gemv_nf4.hip; ``--m`` 5-16: the skinny MFMA GEMM,
+csrc/kernels/gemm_nf4_skinny.hip) on the four quantised projection shapes instead, plain and with
+the r = 64 LoRA epilogue on every sub-projection, as effective TB/s of code bytes
 (N x K / 2 / time), next to the bf16 GEMV and the library GEMM on the dequantised weight.
 """
 import argparse
@@ -66,14 +67,16 @@ def nf4_main(a):
         h = torch.randn(a.m, r * len(spans), device=dev, dtype=torch.bfloat16)
         Bs = [torch.randn(n, r, device=dev, dtype=torch.bfloat16) * 0.05 for _, n in spans]
         offs = [o for o, _ in spans]
-        us = med(lambda: C.nf4_gemv(x, q, am, N, K), a.reps)
-        lus = med(lambda: C.nf4_gemv(x, q, am, N, K, h, Bs, offs, 0.25), a.reps)
+        kern = C.nf4_gemv if a.m <= 4 else C.nf4_gemm_skinny  # 5-16 rows: gemm_nf4_skinny.hip
+        us = med(lambda: kern(x, q, am, N, K), a.reps)
+        lus = med(lambda: kern(x, q, am, N, K, h, Bs, offs, 0.25), a.reps)
         bf = med(lambda: C.gemv(x, w), a.reps)
         lib = med(lambda: torch.nn.functional.linear(x, w), a.reps)
         nb = N * K // 2
         tot += us * 32
         tot_lora += lus * 32
-        print(json.dumps({"shape": name, "N": N, "K": K, "m": a.m, "nf4_gemv_us": round(us, 1),
+        print(json.dumps({"shape": name, "N": N, "K": K, "m": a.m,
+                          "kernel": "nf4_gemv" if a.m <= 4 else "nf4_gemm_skinny", "nf4_gemv_us": round(us, 1),
                           "nf4_gemv_TBps_of_codes": round(nb / us / 1e6, 2), "nf4_gemv_lora_r64_us": round(lus, 1),
                           "bf16_gemv_us": round(bf, 1), "library_us": round(lib, 1)}), flush=True)
         del w, q, am
