@@ -1303,6 +1303,54 @@ Tensor attn_decode_fp8_d64(const Tensor& q, const Tensor& k, const Tensor& v, co
   return attn_decode_fp8_impl(q, k, v, k_scale, v_scale, seqlens_k, scale, 64, "attn_decode_fp8_d64");
 }
 
+// Flash forward over an fp8 cache (prefill_attention_fp8.hip): q bf16 [B, S, Hq, D], the last S of
+// the n keys of k / v (codes [B, n, Hkv, D], views of the cache, with their scales [B, n, Hkv]);
+// token t attends keys [0, n - (S - 1 - t)). One launch, no workspace.
+Tensor attn_prefill_fp8_impl(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& k_scale,
+                             const Tensor& v_scale, double scale, int64_t D, const char* op) {
+  check_cuda(q, "q");
+  TORCH_CHECK(q.dim() == 4 && q.scalar_type() == at::kBFloat16 && q.stride(3) == 1, op, ": q must be bf16 [B, S, Hq, D] "
+              "with unit last stride, got ", q.scalar_type(), " with ", q.dim(), " dims");
+  check_fp8_cache(k, k_scale, q, op, "k");
+  check_fp8_cache(v, v_scale, q, op, "v");
+  TORCH_CHECK(q.size(3) == D && k.size(3) == D && v.size(3) == D, op, ": head_dim ", D, ", got q ", q.size(3), " / k ",
+              k.size(3), " / v ", v.size(3));
+  TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0), op, ": k / v must both be [", q.size(0), ", n, Hkv, ", D, "]");
+  const int64_t S = q.size(1), n = k.size(1), Hq = q.size(2), Hkv = k.size(2);
+  TORCH_CHECK(S >= 1 && n >= S, op, ": the S query tokens are the last S of the n keys, got S = ", S, ", n = ", n);
+  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, op, ": Hq % Hkv, got ", Hq, " / ", Hkv);
+  const int64_t G = Hq / Hkv;
+  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, op, ": GQA group must be 1, 2, 4 or 8, got ", G);
+  TORCH_CHECK(q.stride(0) % 8 == 0 && q.stride(1) % 8 == 0 && q.stride(2) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              op, ": q strides must keep 16-byte alignment");
+  TORCH_CHECK(n <= INT32_MAX - 64 && q.size(0) * S * Hq <= INT32_MAX, op, ": dims");
+  c10::OptionalDeviceGuard g(q.device());
+  auto o = at::empty(q.sizes(), q.options());
+  grt::AttnPrefillFp8Params p{};
+  p.q = q.data_ptr(); p.kc = k.data_ptr(); p.vc = v.data_ptr(); p.o = o.data_ptr();
+  p.k_scale = k_scale.data_ptr<float>(); p.v_scale = v_scale.data_ptr<float>();
+  p.q_bs = q.stride(0); p.q_ss = q.stride(1); p.q_hs = q.stride(2);
+  p.k_bs = k.stride(0); p.k_ss = k.stride(1); p.k_hs = k.stride(2);
+  p.v_bs = v.stride(0); p.v_ss = v.stride(1); p.v_hs = v.stride(2);
+  p.ksc_bs = k_scale.stride(0); p.ksc_ss = k_scale.stride(1); p.ksc_hs = k_scale.stride(2);
+  p.vsc_bs = v_scale.stride(0); p.vsc_ss = v_scale.stride(1); p.vsc_hs = v_scale.stride(2);
+  p.B = (int)q.size(0); p.S = (int)S; p.n = (int)n; p.Hq = (int)Hq; p.Hkv = (int)Hkv;
+  p.scale_log2 = (float)(scale * 1.4426950408889634);
+  grt::attn_prefill_fp8(p, (int)D, cur_stream(q));
+  return o;
+}
+
+Tensor attn_prefill_fp8(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& k_scale, const Tensor& v_scale,
+                        double scale) {
+  return attn_prefill_fp8_impl(q, k, v, k_scale, v_scale, scale, 128, "attn_prefill_fp8");
+}
+
+Tensor attn_prefill_fp8_d64(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& k_scale,
+                            const Tensor& v_scale, double scale) {
+  return attn_prefill_fp8_impl(q, k, v, k_scale, v_scale, scale, 64, "attn_prefill_fp8_d64");
+}
+
 // test support: attn_decode_d64 plus its per-split partial states, [o, part_o [B, Hq, NS, 64],
 // part_m [B, Hq, NS] (log2 units), part_l [B, Hq, NS]]; the partials are written only when NS > 1
 std::vector<Tensor> attn_decode_d64_partials(const Tensor& q, const Tensor& k, const Tensor& v,
@@ -2104,6 +2152,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_d64", &attn_decode_d64);
   m.def("attn_decode_fp8", &attn_decode_fp8);
   m.def("attn_decode_fp8_d64", &attn_decode_fp8_d64);
+  m.def("attn_prefill_fp8", &attn_prefill_fp8);
+  m.def("attn_prefill_fp8_d64", &attn_prefill_fp8_d64);
   m.def("attn_decode_d64_partials", &attn_decode_d64_partials,
         "test support: attn_decode_d64 and its per-split (o, max, sum) partial states");
   m.def("embedding_fwd", &embedding_fwd);

@@ -280,6 +280,21 @@ struct AttnDecodeParams {
 int attn_decode_splits(int B, int Hkv, int Sk, int head_dim = 128);
 void attn_decode(const AttnDecodeParams& p, int head_dim, hipStream_t s);
 void attn_decode_fp8(const AttnDecodeParams& p, int head_dim, hipStream_t s);
+// flash forward over the fp8 cache (prefill_attention_fp8.hip): the chunked prefill. q bf16
+// [B, S, Hq, D] rotated (strided, unit last stride, 16-byte aligned rows), kc / vc e4m3fn codes
+// [B, n, Hkv, D] (strides in bytes, 8-byte aligned) with k_scale / v_scale fp32 [B, n, Hkv], o bf16
+// [B, S, Hq, D] contiguous. The S tokens of a row are the last S of its n keys (n >= S >= 1):
+// token t attends keys [0, n - (S - 1 - t)). Hq / Hkv in {1,2,4,8}, head_dim 128 or 64. One launch,
+// no workspace; slots >= n are never read.
+struct AttnPrefillFp8Params {
+  const void* q; const void* kc; const void* vc; const float* k_scale; const float* v_scale; void* o;
+  int64_t q_bs, q_ss, q_hs;
+  int64_t k_bs, k_ss, k_hs, v_bs, v_ss, v_hs;
+  int64_t ksc_bs, ksc_ss, ksc_hs, vsc_bs, vsc_ss, vsc_hs;
+  int B, S, n, Hq, Hkv;
+  float scale_log2;  // softmax scale * log2(e)
+};
+void attn_prefill_fp8(const AttnPrefillFp8Params& p, int head_dim, hipStream_t s);
 // exact-fp32 variants (attention_f32.hip): same params with fp32 tensors, head_dim 64 or 128
 bool attn_f32_supported(int head_dim);
 void attn_fwd_f32(const AttnParams& p, hipStream_t s);

@@ -2,8 +2,9 @@
 //
 // The cache holds OCP e4m3fn codes [B, L, Hkv, D] (uint8) and one fp32 scale per (token, kv head)
 // [B, L, Hkv]; ops/_ref.py::kv_fp8_quantize defines the format and grt_fp8.h holds the encode. The
-// split-K decode attention kernel reads the codes directly (decode_attention.hip); the dequantiser
-// here serves the chunked-prefill path and the tests.
+// split-K decode attention kernel and the chunked-prefill flash kernel read the codes directly
+// (decode_attention.hip, prefill_attention_fp8.hip); the dequantiser here serves the tests and the
+// benchmark's parent-path arm.
 #include "grt_common.h"
 #include "grt_fp8.h"
 #include "grt_kernels.h"

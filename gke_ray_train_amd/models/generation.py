@@ -52,11 +52,22 @@ so its logits are bitwise those of the bf16 cache. DECODE TOKENS ATTEND TO THEIR
 STORED, that is, quantised: a token's key and value are written before its attention runs, and
 the kernel reads nothing but the cache. In the captured one-token step the qkv GEMV runs without
 its RoPE / append epilogue and ``rope_append_fp8`` follows it: one launch per layer more than the
-bf16 step. A chunk of more than 4 tokens on a non-empty cache (chunked prefill) is a slow path:
-append, dequantise rows [0, n) to bf16 (``kv_fp8_dequant``) and run the flash kernel. Without the
+bf16 step. A chunk of more than 4 tokens on a non-empty cache (chunked prefill) appends its rows and
+runs one flash kernel that reads the codes and scales as stored (``ops.prefill_attention_fp8``,
+prefill_attention_fp8.hip): no bf16 copy of the cache is made, so THE TOKENS OF CHUNK k ATTEND TO
+THE QUANTISED ROWS OF THE CHUNKS BEFORE IT AND OF THEIR OWN CHUNK, and their logits differ from the
+whole-prompt prefill's by the quantisation error of the attention output. Without the
 HIP kernels (CPU, fp32 model, other head dims) the cache is quantised by ``_ref`` and attention
 runs over the dequantised rows. There is no flash-kernel decode path for the fp8 cache:
 ``GRT_DECODE_ATTN=0`` with it is refused wherever it would run on those kernels.
+
+Chunked prefill (``generate(..., prefill_chunk_size=c)``, ``GraphDecoder.prefill(...,
+prefill_chunk_size=c)``): the prompt goes through ``forward_cached`` in consecutive chunks of c
+tokens (the last one shorter) instead of one [B, S] block, which bounds the activations of the
+prefill by B * c rows whatever the prompt length; the logits are those of the last chunk. Both
+cache dtypes take it: over a bf16 cache a chunk runs the flash kernel with Sq < Sk, over an fp8
+cache the kernels above. A padded ``attention_mask`` with it is refused (a ragged prefill is one
+causal block).
 """
 from __future__ import annotations
 
@@ -250,10 +261,9 @@ def _eager_attention_fp8(attn, qkv, B, S, pos0, cos, sin, cache: KVCache, li: in
         elif S <= 4:
             o = ops.decode_attention_fp8(q, cache.k[li][:, :n], cache.v[li][:, :n], cache.k_scale[li][:, :n],
                                          cache.v_scale[li][:, :n], seqlens_k=lens)
-        else:  # chunked prefill, the slow path: a bf16 copy of the rows so far for the flash kernel
-            kk = K.kv_fp8_dequant(cache.k[li], cache.k_scale[li], n)
-            vv = K.kv_fp8_dequant(cache.v[li], cache.v_scale[li], n)
-            o = ops.flash_attention(q, kk, vv, causal=True)
+        else:  # chunked prefill: the flash kernel over the codes and scales as stored
+            o = ops.prefill_attention_fp8(q, cache.k[li][:, :n], cache.v[li][:, :n], cache.k_scale[li][:, :n],
+                                          cache.v_scale[li][:, :n])
         return o.reshape(B * S, hq * D)
     x3 = qkv.view(B * S, hq + 2 * hkv, D)
     q = _ref.apply_rope(x3[:, :hq], cos, sin, pos).view(B, S, hq, D)
@@ -370,6 +380,31 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache, attention_mask=None
             cache.lens = row_pos + 1
     cache.len += S
     return model.lm_head(last).float()
+
+
+def _chunk_size(prefill_chunk_size, rows) -> Optional[int]:
+    """Validate ``prefill_chunk_size`` (``None``: the whole prompt as one block) against the mask."""
+    c = prefill_chunk_size
+    if c is None:
+        return None
+    if isinstance(c, bool) or not isinstance(c, int) or c < 1:
+        raise ValueError(f"prefill_chunk_size must be None or an integer >= 1, got {c!r}")
+    if rows is not None:
+        raise ValueError("prefill_chunk_size with a padded attention_mask: a ragged prefill is one causal block "
+                         "(rows compacted to column 0, logits at each row's own last token) and cannot be chunked")
+    return c
+
+
+def _prefill(model, input_ids: torch.Tensor, cache: KVCache, attention_mask=None, prefill_chunk_size=None):
+    """The prompt through ``forward_cached``: as one block, or with ``prefill_chunk_size`` = c in
+    consecutive chunks of c tokens, the last one shorter; the last chunk's logits are returned."""
+    rows = _mask_rows(attention_mask, *input_ids.shape)
+    c = _chunk_size(prefill_chunk_size, rows)
+    if c is None:
+        return forward_cached(model, input_ids, cache, rows)
+    for i in range(0, input_ids.shape[1], c):
+        logits = forward_cached(model, input_ids[:, i:i + c], cache)
+    return logits
 
 
 _GEMV_NORM = os.environ.get("GRT_GEMV_NORM", "1") != "0"
@@ -595,13 +630,13 @@ class GraphDecoder:
         self._sample(logits)
 
     @torch.no_grad()
-    def prefill(self, input_ids: torch.Tensor, attention_mask=None) -> torch.Tensor:
+    def prefill(self, input_ids: torch.Tensor, attention_mask=None, prefill_chunk_size=None) -> torch.Tensor:
         """Eager prefill. With a padded batch (``attention_mask``, see ``forward_cached``) every
         row then decodes from its own length: the step's position and valid-length tensors differ
-        per row, the captured step itself is the same."""
+        per row, the captured step itself is the same. ``prefill_chunk_size``: see the module doc."""
         if self.spec is not None:
-            return self._spec_prefill(input_ids, attention_mask)
-        logits = forward_cached(self.model, input_ids, self.cache, attention_mask)
+            return self._spec_prefill(input_ids, attention_mask, prefill_chunk_size)
+        logits = _prefill(self.model, input_ids, self.cache, attention_mask, prefill_chunk_size)
         n = self.cache.len
         if self.cache.lens is None:
             self.pos_b.fill_(n)
@@ -612,13 +647,13 @@ class GraphDecoder:
             self.cache.lens = self.pos_b  # the replays advance it
         return logits
 
-    def _spec_prefill(self, input_ids: torch.Tensor, attention_mask=None) -> torch.Tensor:
+    def _spec_prefill(self, input_ids: torch.Tensor, attention_mask=None, prefill_chunk_size=None) -> torch.Tensor:
         """Prefill of the one row (a padded row's tokens are compacted as in ``forward_cached``;
         from then on nothing differs). The positions are left one short of the first verify step's:
         ``first_token`` emits exactly one token and ``spec_advance`` moves them on by it."""
         rows = _mask_rows(attention_mask, 1, input_ids.shape[1])
         prompt = _row_prompt(input_ids, rows)
-        logits = forward_cached(self.model, input_ids, self.cache, rows)
+        logits = _prefill(self.model, input_ids, self.cache, rows, prefill_chunk_size)
         n = prompt.shape[0]
         self.cache.len, self.cache.lens = n, None
         self.prompt_len = n
@@ -753,14 +788,14 @@ last_spec_stats = {"n_replays": 0, "n_emitted": 0}  # of the latest speculative 
 
 
 def _spec_generate(model, input_ids, rows, P: int, sampler: SamplerConfig, spec: SpecConfig, graph: bool,
-                   on_device: bool, sync_every: int, kv=None) -> torch.Tensor:
+                   on_device: bool, sync_every: int, kv=None, chunk=None) -> torch.Tensor:
     """The new tokens [n] of one sequence by prompt-lookup speculative decoding (see ``generate``)."""
     K, new = spec.num_tokens, sampler.max_new_tokens
     dev = input_ids.device
     max_len = P + new + K
     if on_device:
         dec = GraphDecoder(model, 1, max_len, sampler=sampler, spec=spec, kv_cache_dtype=kv)
-        dec.first_token(dec.prefill(input_ids, rows))
+        dec.first_token(dec.prefill(input_ids, rows, chunk))
         left = new - 1  # every replay of a live row emits at least one token
         while left > 0:
             chunk = min(sync_every, left)
@@ -775,13 +810,13 @@ def _spec_generate(model, input_ids, rows, P: int, sampler: SamplerConfig, spec:
     prompt = _row_prompt(input_ids, rows)
     if graph:
         dec = GraphDecoder(model, 1, max_len, spec=spec, kv_cache_dtype=kv)
-        first = dec.prefill(input_ids, rows)
+        first = dec.prefill(input_ids, rows, chunk)
 
         def step(ids, p):
             return dec.step_spec(torch.tensor(ids, device=dev), p)
     else:
         cache = KVCache(model.config, 1, max_len, dev, _kv_dtype(model, kv))
-        first = forward_cached(model, input_ids, cache, rows)
+        first = _prefill(model, input_ids, cache, rows, chunk)
         cache.lens = None  # one row: nothing is ragged once its tokens sit at 0 ... P - 1
 
         def step(ids, p):
@@ -823,7 +858,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              use_graph: Optional[bool] = None, sync_every: int = 16, top_k: Optional[int] = None,
              seed: Optional[int] = None, device_loop: Optional[bool] = None,
              prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: int = 2, _spec_plan=None,
-             kv_cache_dtype: Optional[str] = None, **_):
+             kv_cache_dtype: Optional[str] = None, prefill_chunk_size: Optional[int] = None, **_):
     """Returns [B, prompt + generated] token ids (HF ``generate`` output convention).
 
     ``attention_mask`` [B, S] (bool / integer, HF semantics) batches prompts of unequal length: row
@@ -874,9 +909,17 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     ``"fp8_e4m3"`` stores it as e4m3fn codes with one fp32 scale per (token, kv head), (D + 4) / 2D of
     the bf16 bytes (see the module doc: the prefill logits are those of the bf16 cache, decode
     tokens attend to the quantised cache, the captured one-token step has one more launch per
-    layer, a chunk of more than 4 tokens on a non-empty cache takes a dequantising slow path).
-    Every mode above takes it. ``ValueError``: another value, or ``GRT_DECODE_ATTN=0`` with the fp8
-    cache on the GPU."""
+    layer). Every mode above takes it. ``ValueError``: another value, or ``GRT_DECODE_ATTN=0`` with
+    the fp8 cache on the GPU.
+
+    ``prefill_chunk_size``: ``None`` (default) prefills the whole prompt as one block. An integer
+    c >= 1 feeds it in consecutive chunks of c tokens, the last one shorter, so the prefill's
+    activations are B * c rows whatever the prompt length. Every mode above and both cache dtypes
+    take it. Over a bf16 cache a chunk attends to exactly what the whole block would. Over an fp8
+    cache the tokens of chunk k attend to the QUANTISED rows of the chunks before it and of their
+    own chunk (one flash kernel over the codes, no dequantised copy), so the logits differ from the
+    whole-prompt prefill's by the quantisation error of the attention output. ``ValueError``: c < 1,
+    not an integer, or a padded ``attention_mask`` (a ragged prefill is one causal block)."""
     was = model.training
     model.eval()
     try:
@@ -885,6 +928,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
         _check_fp8_decode(kv == "fp8", input_ids.is_cuda, next(model.parameters()).dtype, model.config.head_dim)
         rows = _mask_rows(attention_mask, B, S)
         P = S if rows is None else max(rows.lens)  # the longest prompt: the cache holds P + max_new_tokens
+        chunk = _chunk_size(prefill_chunk_size, rows)
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
         graph = use_graph if use_graph is not None else _graph_ok(model, input_ids)
         temperature = max(temperature, 1e-5)
@@ -922,22 +966,23 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
         on_device = can and (device_loop if device_loop is not None else _DEVICE_SAMPLER)
         if K and max_new_tokens >= 1:
             new = _spec_generate(model, input_ids, rows, P, sampler, SpecConfig(K, N, _spec_plan), graph, on_device,
-                                 sync_every, kv)[None]
+                                 sync_every, kv, chunk)[None]
         elif on_device:
-            new = _device_loop(model, input_ids, rows, P, sampler, sync_every, kv)
+            new = _device_loop(model, input_ids, rows, P, sampler, sync_every, kv, chunk)
         else:
-            new = _host_loop(model, input_ids, rows, P, sampler, graph, generator, sync_every, kv)
+            new = _host_loop(model, input_ids, rows, P, sampler, graph, generator, sync_every, kv, chunk)
         return torch.cat([input_ids, new], 1)
     finally:
         if was:
             model.train()
 
 
-def _device_loop(model, input_ids, rows, P: int, sampler: SamplerConfig, sync_every: int, kv=None) -> torch.Tensor:
+def _device_loop(model, input_ids, rows, P: int, sampler: SamplerConfig, sync_every: int, kv=None,
+                 chunk=None) -> torch.Tensor:
     """The new tokens [B, n] with the token picked inside the captured step."""
     new, eos = sampler.max_new_tokens, sampler.eos_ids
     dec = GraphDecoder(model, input_ids.shape[0], P + new, sampler=sampler, kv_cache_dtype=kv)
-    dec.first_token(dec.prefill(input_ids, rows))
+    dec.first_token(dec.prefill(input_ids, rows, chunk))
     done = 1
     while done < new:
         # replays up to the next multiple of sync_every tokens, then one host read
@@ -968,16 +1013,17 @@ def _multinomial_pick(logits, temperature: float, top_k: int, top_p: float, gene
     return torch.multinomial(probs / probs.sum(-1, keepdim=True), 1, generator=generator).squeeze(-1)
 
 
-def _host_loop(model, input_ids, rows, P: int, c: SamplerConfig, graph: bool, generator, sync_every: int, kv=None):
+def _host_loop(model, input_ids, rows, P: int, c: SamplerConfig, graph: bool, generator, sync_every: int, kv=None,
+               chunk=None):
     """The new tokens [B, n], picked on the host from the logits of the graph's or the eager step."""
     B, new = input_ids.shape[0], c.max_new_tokens
     if graph:
         dec = GraphDecoder(model, B, P + new, kv_cache_dtype=kv)
-        logits = dec.prefill(input_ids, rows)
+        logits = dec.prefill(input_ids, rows, chunk)
         forward = dec.step
     else:
         cache = KVCache(model.config, B, P + new, input_ids.device, _kv_dtype(model, kv))
-        logits = forward_cached(model, input_ids, cache, rows)
+        logits = _prefill(model, input_ids, cache, rows, chunk)
 
         def forward(nxt):
             return forward_cached(model, nxt[:, None], cache)

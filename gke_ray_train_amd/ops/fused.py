@@ -330,6 +330,27 @@ def decode_attention_fp8(q, kc, vc, k_scale, v_scale, seqlens_k=None, scale=None
     return torch.cat(out, 1)
 
 
+def prefill_attention_fp8(q, kc, vc, k_scale, v_scale, scale=None):
+    """Causal attention of a prefill chunk over an fp8 KV cache: q [B, S, Hq, D] bf16, the S >= 1 new
+    tokens of every row, whose keys are the last S of the n that kc / vc [B, n, Hkv, D] (uint8 e4m3fn
+    codes, views of the cache) and k_scale / v_scale [B, n, Hkv] (fp32, ``_ref.kv_fp8_quantize``)
+    hold: token t attends keys [0, n - (S - 1 - t)), ``decode_attention_fp8``'s rule for any S. On
+    the GPU one flash kernel reads the codes and scales as stored (prefill_attention_fp8.hip: bf16,
+    head_dim 128 or 64, Hq / Hkv in {1, 2, 4, 8}; anything else is an error); no dequantised copy
+    is made. The CPU dequantises and takes the math path, whose causal offset n - S is this rule."""
+    D = q.shape[-1]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if _gpu(q):
+        if q.dtype != torch.bfloat16 or D not in (64, 128):
+            raise ValueError(f"prefill_attention_fp8: no gfx950 kernel for {q.dtype} with head_dim {D} "
+                             "(bf16, head_dim 64 or 128)")
+        C = _native.kernels()
+        return (C.attn_prefill_fp8 if D == 128 else C.attn_prefill_fp8_d64)(q, kc, vc, k_scale, v_scale, scale)
+    k = _ref.kv_fp8_dequantize(kc, k_scale, q.dtype)
+    v = _ref.kv_fp8_dequantize(vc, v_scale, q.dtype)
+    return _ref.attention(q, k, v, causal=True, scale=scale)
+
+
 _warned = set()
 
 
