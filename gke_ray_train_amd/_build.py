@@ -69,11 +69,13 @@ def _check_flags():
     return ["-DGRT_KERNEL_CHECKS=1"] if os.environ.get("GRT_KERNEL_CHECKS", "0") == "1" else []
 
 
-# Extra hipcc flags of single kernel files. gemm_nf4_skinny: no packed fp32 instructions (the
-# compiler would form v_pk_fma_f32 from the per-block absmax FMAs on the accumulator tile);
+# Extra hipcc flags of single kernel files. gemm_nf4_skinny, gemm_nf4_tile: no packed fp32
+# instructions (the compiler would form v_pk_fma_f32 from the per-block absmax FMAs on the
+# accumulator tile);
 # prefill_attention_fp8: likewise (v_pk_mul_f32 from the rescale of the output accumulators).
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-KERNEL_FLAGS = {"gemm_nf4_skinny": _NO_PACKED_FP32, "prefill_attention_fp8": _NO_PACKED_FP32}
+KERNEL_FLAGS = {"gemm_nf4_skinny": _NO_PACKED_FP32, "gemm_nf4_tile": _NO_PACKED_FP32,
+                "prefill_attention_fp8": _NO_PACKED_FP32}
 
 
 def build_kernels(force=False, jobs=8, verbose=False) -> Path:

@@ -1719,12 +1719,17 @@ void spec_advance(const Tensor& cand, const Tensor& drafts, const Tensor& ids, c
 // 1-4 rows. With h [M, r * targets], lora_b (target i: bf16 [n_i, r]) and lora_off (its first output
 // row): rows of target i also get scaling * h[:, i r : (i + 1) r] lora_b[i]^T.
 // nf4_gemm_skinny: the same for 1-16 rows on the MFMA kernel (gemm_nf4_skinny.hip), whose 16-byte
-// loads of h and lora_b add two alignment checks; nf4_matmul holds the checks and the launch of both.
-static Tensor nf4_matmul(const char* what, bool skinny, const Tensor& x, const Tensor& q, const Tensor& absmax,
+// loads of h and lora_b add two alignment checks. nf4_gemm_tile: the same for 1-256 rows on the tile
+// kernel (gemm_nf4_tile.hip), with the skinny kernel's checks; k_split K ranges (0: the host's choice),
+// whose fp32 partial tiles go through a workspace. nf4_matmul holds the checks and the launch of all three.
+enum class Nf4Kernel { Gemv, Skinny, Tile };
+static Tensor nf4_matmul(const char* what, Nf4Kernel kernel, const Tensor& x, const Tensor& q, const Tensor& absmax,
                          int64_t N, int64_t K, const optional<Tensor>& h,
                          const optional<std::vector<Tensor>>& lora_b,
-                         const optional<std::vector<int64_t>>& lora_off, double scaling) {
-  const int64_t max_rows = skinny ? grt::kNf4SkinnyMaxRows : 4;
+                         const optional<std::vector<int64_t>>& lora_off, double scaling, int64_t k_split = 0) {
+  const bool skinny = kernel != Nf4Kernel::Gemv;  // the MFMA kernels' 16-byte loads of h and lora_b
+  const int64_t max_rows = kernel == Nf4Kernel::Tile ? grt::kNf4TileMaxRows
+                           : kernel == Nf4Kernel::Skinny ? grt::kNf4SkinnyMaxRows : 4;
   check_cuda(x, "x");
   check_contig(q, "qweight");
   check_contig(absmax, "absmax");
@@ -1770,21 +1775,37 @@ static Tensor nf4_matmul(const char* what, bool skinny, const Tensor& x, const T
   c10::OptionalDeviceGuard g(x.device());
   Tensor y = at::empty({M, N}, x.options());
   f.y = y.data_ptr();
-  if (skinny) grt::gemm_nf4_skinny(f, cur_stream(x));
-  else grt::gemv_nf4(f, cur_stream(x));
+  if (kernel == Nf4Kernel::Tile) {
+    TORCH_CHECK(k_split >= 0 && k_split <= K / 64, what, ": k_split in 0..K / 64");
+    const grt::Nf4TileSplit split = grt::gemm_nf4_tile_split((int)M, (int)N, (int)K, (int)k_split);
+    TORCH_CHECK(split.splits >= 1, what, ": k_split ", k_split, " leaves a split empty (", K / 64, " quant blocks)");
+    Tensor ws;
+    if (split.splits > 1) ws = at::empty({split.splits, M, N}, x.options().dtype(at::kFloat));
+    grt::gemm_nf4_tile(f, split, split.splits > 1 ? ws.data_ptr<float>() : nullptr, cur_stream(x));
+  } else if (kernel == Nf4Kernel::Skinny) {
+    grt::gemm_nf4_skinny(f, cur_stream(x));
+  } else {
+    grt::gemv_nf4(f, cur_stream(x));
+  }
   return y;
 }
 
 Tensor nf4_gemv(const Tensor& x, const Tensor& q, const Tensor& absmax, int64_t N, int64_t K,
                 const optional<Tensor>& h, const optional<std::vector<Tensor>>& lora_b,
                 const optional<std::vector<int64_t>>& lora_off, double scaling) {
-  return nf4_matmul("nf4_gemv", false, x, q, absmax, N, K, h, lora_b, lora_off, scaling);
+  return nf4_matmul("nf4_gemv", Nf4Kernel::Gemv, x, q, absmax, N, K, h, lora_b, lora_off, scaling);
 }
 
 Tensor nf4_gemm_skinny(const Tensor& x, const Tensor& q, const Tensor& absmax, int64_t N, int64_t K,
                        const optional<Tensor>& h, const optional<std::vector<Tensor>>& lora_b,
                        const optional<std::vector<int64_t>>& lora_off, double scaling) {
-  return nf4_matmul("nf4_gemm_skinny", true, x, q, absmax, N, K, h, lora_b, lora_off, scaling);
+  return nf4_matmul("nf4_gemm_skinny", Nf4Kernel::Skinny, x, q, absmax, N, K, h, lora_b, lora_off, scaling);
+}
+
+Tensor nf4_gemm_tile(const Tensor& x, const Tensor& q, const Tensor& absmax, int64_t N, int64_t K,
+                     const optional<Tensor>& h, const optional<std::vector<Tensor>>& lora_b,
+                     const optional<std::vector<int64_t>>& lora_off, double scaling, int64_t k_split) {
+  return nf4_matmul("nf4_gemm_tile", Nf4Kernel::Tile, x, q, absmax, N, K, h, lora_b, lora_off, scaling, k_split);
 }
 
 // ------------------------------------------------------------------ embedding
@@ -2136,6 +2157,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nf4_gemm_skinny", &nf4_gemm_skinny, py::arg("x"), py::arg("qweight"), py::arg("absmax"), py::arg("N"),
         py::arg("K"), py::arg("h") = py::none(), py::arg("lora_b") = py::none(), py::arg("lora_off") = py::none(),
         py::arg("scaling") = 1.0);
+  m.def("nf4_gemm_tile", &nf4_gemm_tile, py::arg("x"), py::arg("qweight"), py::arg("absmax"), py::arg("N"),
+        py::arg("K"), py::arg("h") = py::none(), py::arg("lora_b") = py::none(), py::arg("lora_off") = py::none(),
+        py::arg("scaling") = 1.0, py::arg("k_split") = 0);
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("do_sample") = false, py::arg("temperature") = 1.0,
         py::arg("top_k") = 0, py::arg("top_p") = 1.0, py::arg("seed") = 0, py::arg("counter") = py::none(),
         py::arg("keep_mask") = py::none(), py::arg("finished") = py::none(), py::arg("finish_step") = py::none(),

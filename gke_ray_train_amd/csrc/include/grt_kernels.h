@@ -467,6 +467,22 @@ using Nf4GemmSkinny = Nf4Gemv;
 constexpr int kNf4SkinnyMaxRows = 16;
 void gemm_nf4_skinny(const Nf4GemmSkinny& f, hipStream_t s);
 
+// ---------------- tile MFMA GEMM from NF4 codes (gemm_nf4_tile.hip) ----------------
+// The same operation, arguments, numerics and alignment conditions for M <= 256 (prefill chunks):
+// 128 weight rows x 32 / 64 / 128 activation rows per workgroup, x staged once per tile in LDS, K
+// split over workgroups. gemm_nf4_tile_split plans the split: k_split = 0 is the host's choice (the
+// grid fills the chip about once, no split under 8 quant blocks), k_split > 0 the caller's, refused
+// (splits = 0) when ceil(blocks / k_split) blocks each would leave the last split empty. With
+// splits > 1 the caller supplies ws, fp32 [splits, M, N]; the splits are added in index order by a
+// second kernel (no atomics).
+using Nf4GemmTile = Nf4Gemv;
+constexpr int kNf4TileMaxRows = 256;
+struct Nf4TileSplit {
+  int splits, per;  // K ranges, and quant blocks in each but the last, which runs to K
+};
+Nf4TileSplit gemm_nf4_tile_split(int M, int N, int K, int k_split);
+void gemm_nf4_tile(const Nf4GemmTile& f, Nf4TileSplit split, float* ws, hipStream_t s);
+
 // ---------------- token sampler (sample.hip) ----------------
 // One token per row of logits [B, V] (bf16 / fp32, row stride ld elements): greedy argmax, or a
 // Gumbel-max draw over the top-k / top-p kept set of logits * inv_t (semantics and the noise

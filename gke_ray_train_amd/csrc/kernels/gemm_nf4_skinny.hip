@@ -33,19 +33,16 @@
 // order of the target list does not change a bit. Then acc += s * acc_lora.
 #include "grt_common.h"
 #include "grt_kernels.h"
+#include "grt_nf4_table.h"
 
 namespace grt {
 namespace {
 
+using nf4_table::decode8;
+
 constexpr int kU = 4;  // quant blocks per lane and K step: 4 x 8 B of codes in flight, twice (prefetch)
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__constant__ float kLevels[16] = {
-    -1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f,
-    -0.28444138169288635f, -0.18477343022823334f, -0.09105003625154495f, 0.0f,
-    0.07958029955625534f, 0.16093020141124725f, 0.24611230194568634f, 0.33791524171829224f,
-    0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f, 1.0f};
 
 struct SkinnyArgs {
   const bf16* x;
@@ -62,29 +59,6 @@ struct SkinnyArgs {
   const bf16* b[kNf4GemvMaxTargets];  // lora_B [n_i, r] contiguous
   int off[kNf4GemvMaxTargets], n[kNf4GemvMaxTargets];
 };
-
-// byte offset of the table row of the code at bits S .. S + 3 of w (a row is 32 slots = 128 bytes)
-template <int S>
-__device__ __forceinline__ uint32_t row_off(uint32_t w) {
-  return (S >= 7 ? w >> (S >= 7 ? S - 7 : 0) : w << (S < 7 ? 7 - S : 0)) & 0x780u;
-}
-
-// The table is 2 KiB-aligned in LDS, so a slot's address is (row offset) | col with col = the LDS
-// address of the lane's column in row 0: one v_and_or_b32 (as pointer + offset the compiler emits
-// an and and an add).
-typedef __attribute__((address_space(3))) const uint32_t* LdsSlot;
-
-// 8 codes (one 32-bit word: byte j holds element 2j in its high nibble, 2j + 1 in its low) -> 8 bf16
-template <int J>
-__device__ __forceinline__ uint32_t decode2(uint32_t w, uint32_t col) {
-  const uint32_t e = *reinterpret_cast<LdsSlot>(row_off<8 * J + 4>(w) | col);
-  const uint32_t o = *reinterpret_cast<LdsSlot>(row_off<8 * J>(w) | col);
-  return e | (o << 16);
-}
-__device__ __forceinline__ bf16x8 decode8(uint32_t w, uint32_t col) {
-  const u32x4 d = {decode2<0>(w, col), decode2<1>(w, col), decode2<2>(w, col), decode2<3>(w, col)};
-  return __builtin_bit_cast(bf16x8, d);
-}
 
 struct Step {  // one K step of a lane: kU quant blocks
   u32x2 q[kU];
@@ -126,10 +100,9 @@ __global__ __launch_bounds__(64 * KS) void gemm_nf4_skinny_kernel(const SkinnyAr
   Step cur, nxt;
   int k = wave * 64 * kU;
   if (k < K) load(k, cur);
-  for (int i = threadIdx.x; i < 16 * 32; i += 64 * KS)
-    tab[i] = __builtin_bit_cast(unsigned short, static_cast<bf16>(kLevels[i >> 5]));
+  nf4_table::fill<64 * KS>(tab);
   __syncthreads();
-  const uint32_t col = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsSlot)(tab + (lane & 31))));
+  const uint32_t col = nf4_table::column(tab, lane);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   while (k < K) {
     const int kn = k + KS * 64 * kU;

@@ -71,7 +71,6 @@ causal block).
 """
 from __future__ import annotations
 
-import contextlib
 import os
 from dataclasses import dataclass
 from typing import List, Optional, Tuple, Union
@@ -80,7 +79,7 @@ import torch
 
 from .. import _native, ops
 from ..ops import _ref
-from ..peft.quant import decode_step
+from ..peft.quant import decode_step, prefill_step
 
 
 KV_CACHE_DTYPES = (None, "auto", "fp8", "fp8_e4m3")
@@ -361,8 +360,10 @@ def forward_cached(model, ids: torch.Tensor, cache: KVCache, attention_mask=None
     cos, sin = model.rope(cache.max_len, ids.device)
     h = model.model.embed_tokens(ids).view(B * S, -1)
     # one token (or one verify chunk) per sequence on top of a cache is a decode step: an NF4 base
-    # may take its B * S rows from the codes (peft/quant.py decode_step); a prefill never is
-    step = decode_step(B * S) if (pos0 > 0 or row_pos is not None) and S <= 4 else contextlib.nullcontext()
+    # may take its B * S rows from the codes (peft/quant.py decode_step); every other call is a
+    # prefill (chunk), whose rows an NF4 base without the dequant cache may take from the codes too
+    # (17+ rows, or 5+ for a later chunk of a chunked prefill)
+    step = decode_step(B * S) if (pos0 > 0 or row_pos is not None) and S <= 4 else prefill_step(B * S, continued=pos0 > 0)
     with step:
         x = _layers(model, h,
                     lambda li, attn, qkv: _eager_attention(attn, qkv, B, S, pos0, cos, sin, cache, li, row_pos))

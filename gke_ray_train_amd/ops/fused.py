@@ -659,3 +659,16 @@ def nf4_gemm_skinny(x, qweight, absmax, N, K, h=None, lora_b=None, lora_off=None
             return _native.kernels().nf4_gemm_skinny(x, qweight, absmax, N, K)
         return _native.kernels().nf4_gemm_skinny(x, qweight, absmax, N, K, h, list(lora_b), list(lora_off), scaling)
     return _ref.nf4_gemv(x, qweight, absmax, N, K, h, lora_b, lora_off, scaling)
+
+
+def nf4_gemm_tile(x, qweight, absmax, N, K, h=None, lora_b=None, lora_off=None, scaling=1.0, k_split=0):
+    """``nf4_gemm_skinny`` for 1-256 bf16 rows on the tile MFMA kernel (gemm_nf4_tile.hip): a prefill
+    chunk straight from the codes, the same numerics and alignment conditions. ``k_split`` K ranges
+    (0: chosen so that the grid fills the chip) whose fp32 partial tiles are added in index order;
+    refused when a range would be empty. Off the GPU: the float reference, which takes any M."""
+    if _gpu(x):
+        if lora_b is None:
+            return _native.kernels().nf4_gemm_tile(x, qweight, absmax, N, K, k_split=k_split)
+        return _native.kernels().nf4_gemm_tile(x, qweight, absmax, N, K, h, list(lora_b), list(lora_off), scaling,
+                                               k_split)
+    return _ref.nf4_gemv(x, qweight, absmax, N, K, h, lora_b, lora_off, scaling)

@@ -530,10 +530,11 @@ class LoraLinear(nn.Module):
         return list(range(len(As))), c[1]
 
     def _decode_forward(self, x) -> Optional[torch.Tensor]:
-        """Decode step on an NF4 base (1-4 rows, or a declared ``decode_step`` of 5-16; no autograd,
-        dropout inactive): h = gemv(x, A_cat), then ONE product from the codes whose epilogue adds
-        every target's s * h_i B_i^T (csrc/kernels/gemv_nf4.hip, gemm_nf4_skinny.hip). None when it
-        does not apply: the caller takes ``_LoraFn``."""
+        """Decode step on an NF4 base (1-4 rows, or a declared ``decode_step`` of 5-16) or, without
+        the dequant cache, a declared ``prefill_step`` of 17-256 rows; no autograd, dropout inactive:
+        h = gemv(x, A_cat) (the library GEMM above 16 rows), then ONE product from the codes whose
+        epilogue adds every target's s * h_i B_i^T (csrc/kernels/gemv_nf4.hip, gemm_nf4_skinny.hip,
+        gemm_nf4_tile.hip). None when it does not apply: the caller takes ``_LoraFn``."""
         b = self.base
         k = len(self.targets)
         if not (isinstance(b, NF4Linear) and 1 <= k <= 4 and 8 <= self.r <= 64 and self.r % 8 == 0
@@ -552,9 +553,9 @@ class LoraLinear(nn.Module):
         if acat.data_ptr() % 16 != 0:
             return None
         rows = x2.shape[0]
-        if rows > 4 and any(t.data_ptr() % 16 != 0 for t in Bs):  # the skinny GEMM's 16-byte loads
+        if rows > 4 and any(t.data_ptr() % 16 != 0 for t in Bs):  # the MFMA kernels' 16-byte loads
             return None
-        if rows <= 4 or self.in_features % 256 == 0:           # the bf16 GEMV family's domain (gemv_mfma_ok)
+        if rows <= 4 or (rows <= 16 and self.in_features % 256 == 0):  # the bf16 GEMV family's domain (gemv_mfma_ok)
             h = _native.kernels().gemv(x2, acat)               # [rows, r * k], column block j = target order[j]
         else:
             h = F.linear(x2, acat)

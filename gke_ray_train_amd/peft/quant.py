@@ -11,7 +11,9 @@ with one fp32 scale per 256 blocks (bitsandbytes' nested quantisation) and expan
 
 Decode (no autograd) multiplies straight from the codes instead: 1-4 rows on the NF4 GEMV
 (csrc/kernels/gemv_nf4.hip), and the 5-16 rows of a batched decode step, declared by the caller with
-``decode_step(rows)``, on the skinny MFMA GEMM (csrc/kernels/gemm_nf4_skinny.hip).
+``decode_step(rows)``, on the skinny MFMA GEMM (csrc/kernels/gemm_nf4_skinny.hip). A layer without
+the dequant cache also takes the 17-256 rows of a declared prefill chunk (``prefill_step(rows)``) from
+the codes, on the tile MFMA GEMM (csrc/kernels/gemm_nf4_tile.hip).
 """
 from __future__ import annotations
 
@@ -65,6 +67,24 @@ NF4_SKINNY_KERNEL_ROWS = 16
 NF4_SKINNY_MAX_ROWS = min(int(os.environ.get("GRT_NF4_SKINNY_MAX_ROWS", NF4_SKINNY_KERNEL_ROWS)),
                           NF4_SKINNY_KERNEL_ROWS)
 _decode_rows = 0  # rows of the declared decode step, 0 outside one
+# Prefill chunks (17-256 rows) of a layer WITHOUT the dequant cache: the tile MFMA GEMM from the codes
+# (csrc/kernels/gemm_nf4_tile.hip) instead of rebuilding a bf16 W per projection and chunk. As for
+# the skinny GEMM the row count alone does not select it: the caller declares the forward a prefill
+# of that many rows with ``prefill_step`` (models/generation.py forward_cached does). A later chunk of a
+# chunked prefill may be shorter (40 tokens in chunks of 24 end with 16): declared as ``continued``,
+# its 5-16 rows go through the same kernel, so that a chunked prefill never builds a bf16 W; a first
+# chunk or a whole prompt of up to 16 rows dequantises as before. A layer with the cache on keeps the
+# library GEMM on its resident W (a per-shape choice against it is unmeasured).
+# Row limit: 128, below the kernel's own 256. Llama-3.1-8B QLoRA r = 64, cache off, prefill of 2,048
+# tokens at batch 1 in chunks of 32 / 64 / 128 / 256, arms alternating in one process, two rounds:
+# 0.606-0.627 / 0.340 / 0.188-0.189 / 0.143 s from the codes against 1.192-1.218 / 0.589-0.611 /
+# 0.295-0.305 / 0.138-0.144 s dequantising per chunk (profiles/nf4_decode.md): 1.6-2.0x up to 128 rows,
+# a tie inside the round-to-round spread at 256 (two row passes decode every weight twice).
+# GRT_NF4_TILE_MAX_ROWS sets the limit, at most the kernel's 256; 16 turns the path off.
+NF4_TILE_KERNEL_ROWS = 256
+NF4_TILE_MAX_ROWS = min(int(os.environ.get("GRT_NF4_TILE_MAX_ROWS", 128)), NF4_TILE_KERNEL_ROWS)
+_prefill_rows = 0  # rows of the declared prefill chunk, 0 outside one
+_prefill_continued = False  # the declared chunk continues a prefill (the cache holds earlier chunks)
 
 
 @contextlib.contextmanager
@@ -80,8 +100,27 @@ def decode_step(rows: int):
         _decode_rows = prev
 
 
+@contextlib.contextmanager
+def prefill_step(rows: int, continued: bool = False):
+    """Declare the forwards inside as one prefill chunk of ``rows`` activation rows (sequences x
+    tokens of the chunk). ``continued``: the chunk goes on top of a filled cache, so it is a later
+    chunk of a chunked prefill; its 5-16 rows (a short last chunk) then stay on the codes as well."""
+    global _prefill_rows, _prefill_continued
+    prev, _prefill_rows, _prefill_continued = (_prefill_rows, _prefill_continued), int(rows), bool(continued)
+    try:
+        yield
+    finally:
+        _prefill_rows, _prefill_continued = prev
+
+
 def _skinny_rows(rows: int) -> bool:
     return NF4_GEMV_KERNEL_ROWS < rows <= NF4_SKINNY_MAX_ROWS and rows == _decode_rows
+
+
+def _tile_rows(rows: int) -> bool:
+    least = NF4_GEMV_KERNEL_ROWS if _prefill_continued and NF4_TILE_MAX_ROWS > NF4_SKINNY_KERNEL_ROWS \
+        else NF4_SKINNY_KERNEL_ROWS
+    return least < rows <= NF4_TILE_MAX_ROWS and rows == _prefill_rows
 
 
 class _NF4Matmul(torch.autograd.Function):
@@ -167,13 +206,16 @@ class NF4Linear(nn.Module):
     def gemv_input(self, x: torch.Tensor) -> Optional[torch.Tensor]:
         """``x`` as the [rows, in_features] view the NF4 kernels take, or None when neither decode
         kernel applies (autograd on, not the GPU / bf16 / blocksize-64 format, in_features % 64,
-        more rows than the GEMV's limit and no declared ``decode_step`` of exactly that many rows
-        within the skinny GEMM's limit, unaligned rows): the caller then takes the dequantising path."""
+        more rows than the GEMV's limit and neither a declared ``decode_step`` of exactly that many
+        rows within the skinny GEMM's limit nor, with the dequant cache off, a declared
+        ``prefill_step`` of exactly that many rows within the tile GEMM's, unaligned rows): the
+        caller then takes the dequantising path."""
         K = self.in_features
         if not (_NF4_GEMV and not torch.is_grad_enabled() and x.is_cuda and self.qweight.is_cuda
                 and self.compute_dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and self.blocksize == 64
                 and K % 64 == 0 and x.shape[-1] == K and x.numel() > 0
-                and (x.numel() // K <= NF4_GEMV_MAX_ROWS or _skinny_rows(x.numel() // K))):
+                and (x.numel() // K <= NF4_GEMV_MAX_ROWS or _skinny_rows(x.numel() // K)
+                     or (_tile_rows(x.numel() // K) and not getattr(self, "_cache_on", False)))):
             return None
         x2 = x.reshape(-1, K)
         if x2.stride(1) != 1 or x2.stride(0) % 8 != 0 or x2.stride(0) < K or x2.data_ptr() % 16 != 0 \
@@ -183,8 +225,11 @@ class NF4Linear(nn.Module):
 
     def codes_matmul(self, x2: torch.Tensor, h=None, lora_b=None, lora_off=None, scaling=1.0) -> torch.Tensor:
         """y = x2 W^T (+ the LoRA epilogue) from the codes, ``x2`` from ``gemv_input``: 1-4 rows on
-        the GEMV, a declared decode step of 5-16 rows on the skinny MFMA GEMM."""
-        fn = ops.nf4_gemv if x2.shape[0] <= NF4_GEMV_KERNEL_ROWS else ops.nf4_gemm_skinny
+        the GEMV, a declared decode step of 5-16 rows on the skinny MFMA GEMM, a declared prefill
+        chunk of 17-256 rows (5-256 for a continued one) on the tile MFMA GEMM."""
+        rows = x2.shape[0]
+        fn = ops.nf4_gemv if rows <= NF4_GEMV_KERNEL_ROWS else \
+            ops.nf4_gemm_skinny if _skinny_rows(rows) else ops.nf4_gemm_tile
         return fn(x2, self.qweight, self._absmax_f32(), self.out_features, self.in_features, h, lora_b, lora_off,
                   scaling)
 

@@ -9,9 +9,11 @@ per shape.
     python tools/gemv_bench.py [--m 1] [--reps 50] [--flush]
 
 ``--nf4``: the NF4 GEMV (csrc/kernels/gemv_nf4.hip; ``--m`` 5-16: the skinny MFMA GEMM,
-csrc/kernels/gemm_nf4_skinny.hip) on the four quantised projection shapes instead, plain and with
-the r = 64 LoRA epilogue on every sub-projection, as effective TB/s of code bytes
-(N x K / 2 / time), next to the bf16 GEMV and the library GEMM on the dequantised weight.
+csrc/kernels/gemm_nf4_skinny.hip; ``--m`` 17-256: the tile MFMA GEMM, csrc/kernels/gemm_nf4_tile.hip)
+on the four quantised projection shapes instead, plain and with the r = 64 LoRA epilogue on every
+sub-projection, as effective TB/s of code bytes (N x K / 2 / time), next to the bf16 GEMV (up to 16
+rows), the library GEMM on the dequantised weight and ``nf4_dequantize`` followed by that GEMM (what
+a prefill chunk costs without the dequant cache).
 """
 import argparse
 import json
@@ -67,18 +69,22 @@ def nf4_main(a):
         h = torch.randn(a.m, r * len(spans), device=dev, dtype=torch.bfloat16)
         Bs = [torch.randn(n, r, device=dev, dtype=torch.bfloat16) * 0.05 for _, n in spans]
         offs = [o for o, _ in spans]
-        kern = C.nf4_gemv if a.m <= 4 else C.nf4_gemm_skinny  # 5-16 rows: gemm_nf4_skinny.hip
+        kname = "nf4_gemv" if a.m <= 4 else "nf4_gemm_skinny" if a.m <= 16 else "nf4_gemm_tile"
+        kern = getattr(C, kname)
         us = med(lambda: kern(x, q, am, N, K), a.reps)
         lus = med(lambda: kern(x, q, am, N, K, h, Bs, offs, 0.25), a.reps)
-        bf = med(lambda: C.gemv(x, w), a.reps)
+        bf = med(lambda: C.gemv(x, w), a.reps) if a.m <= 16 else None
         lib = med(lambda: torch.nn.functional.linear(x, w), a.reps)
+        deq = med(lambda: torch.nn.functional.linear(
+            x, ops.nf4_dequantize(q, am, N * K, 64, torch.bfloat16).view(N, K)), a.reps)
         nb = N * K // 2
         tot += us * 32
         tot_lora += lus * 32
         print(json.dumps({"shape": name, "N": N, "K": K, "m": a.m,
-                          "kernel": "nf4_gemv" if a.m <= 4 else "nf4_gemm_skinny", "nf4_gemv_us": round(us, 1),
+                          "kernel": kname, "nf4_gemv_us": round(us, 1),
                           "nf4_gemv_TBps_of_codes": round(nb / us / 1e6, 2), "nf4_gemv_lora_r64_us": round(lus, 1),
-                          "bf16_gemv_us": round(bf, 1), "library_us": round(lib, 1)}), flush=True)
+                          "bf16_gemv_us": bf and round(bf, 1), "library_us": round(lib, 1),
+                          "dequantize_then_library_us": round(deq, 1)}), flush=True)
         del w, q, am
     print(json.dumps({"nf4_projections_per_token_ms": round(tot / 1e3, 3),
                       "with_lora_epilogue_ms": round(tot_lora / 1e3, 3)}), flush=True)
