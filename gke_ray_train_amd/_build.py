@@ -72,10 +72,11 @@ def _check_flags():
 # Extra hipcc flags of single kernel files. gemm_nf4_skinny, gemm_nf4_tile: no packed fp32
 # instructions (the compiler would form v_pk_fma_f32 from the per-block absmax FMAs on the
 # accumulator tile);
-# prefill_attention_fp8: likewise (v_pk_mul_f32 from the rescale of the output accumulators).
+# prefill_attention_fp8: likewise (v_pk_mul_f32 from the rescale of the output accumulators);
+# gemv_mfma_fused: likewise (v_pk_mul_f32 from the norm / SwiGLU products of the A fragments).
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 KERNEL_FLAGS = {"gemm_nf4_skinny": _NO_PACKED_FP32, "gemm_nf4_tile": _NO_PACKED_FP32,
-                "prefill_attention_fp8": _NO_PACKED_FP32}
+                "prefill_attention_fp8": _NO_PACKED_FP32, "gemv_mfma_fused": _NO_PACKED_FP32}
 
 
 def build_kernels(force=False, jobs=8, verbose=False) -> Path:

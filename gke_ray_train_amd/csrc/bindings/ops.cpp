@@ -1506,23 +1506,30 @@ Tensor gemv(const Tensor& x, const Tensor& w, bool swiglu) {
 //   cos given (qkv, head_dim D = 2 * cos.size(-1), 128 or 64): RoPE in the epilogue at position
 //   pos[m]; returns q [M, hq, D], k / v written to cache slot pos[m] of kc / vc (rope_append
 //   semantics: bad positions write nothing).
-Tensor gemv_fused(const Tensor& x, const Tensor& w, const Tensor& sumsq, int64_t slot, bool swiglu,
-                  const c10::optional<Tensor>& g, const c10::optional<Tensor>& res, double eps,
-                  const c10::optional<Tensor>& cos, const c10::optional<Tensor>& sin, const c10::optional<Tensor>& pos,
-                  const c10::optional<Tensor>& kc, const c10::optional<Tensor>& vc, int64_t hq, int64_t hkv) {
+// gemv_fused: 1..4 rows on the FMA kernel; gemv_mfma_fused: 3..16 rows with K % 256 == 0 on the MFMA
+// skinny kernel, the same arguments and contracts (mfma picks; name = "<binding>: " for the messages).
+static Tensor gemv_fused_impl(const char* name, bool mfma, const Tensor& x, const Tensor& w, const Tensor& sumsq,
+                              int64_t slot, bool swiglu, const c10::optional<Tensor>& g,
+                              const c10::optional<Tensor>& res, double eps, const c10::optional<Tensor>& cos,
+                              const c10::optional<Tensor>& sin, const c10::optional<Tensor>& pos,
+                              const c10::optional<Tensor>& kc, const c10::optional<Tensor>& vc, int64_t hq,
+                              int64_t hkv) {
   check_cuda(x, "x");
   check_contig(w, "w");
   check_contig(sumsq, "sumsq");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == (swiglu ? 2 : 1) * w.size(1), "gemv_fused: x [M, K], w [N, K]");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "gemv_fused: bf16");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == (swiglu ? 2 : 1) * w.size(1), name, "x [M, K], w [N, K]");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, name, "bf16");
   const int64_t M = x.size(0), N = w.size(0), K = w.size(1);
-  TORCH_CHECK(M >= 1 && M <= 4 && K % 8 == 0 && x.stride(1) == 1 && x.stride(0) % 8 == 0, "gemv_fused: 1..4 rows, K % 8");
-  TORCH_CHECK(N <= INT32_MAX && K <= INT32_MAX, "gemv_fused: dims");
+  TORCH_CHECK(mfma || (M >= 1 && M <= 4), name, "1..4 rows");
+  TORCH_CHECK(!mfma || (M <= 16 && K <= INT32_MAX && grt::gemv_mfma_ok((int)M, (int)K)), name,
+              "3..16 rows, K % 256 == 0 (rows ", M, ", K ", K, ")");
+  TORCH_CHECK(K % 8 == 0 && x.stride(1) == 1 && x.stride(0) % 8 == 0, name, "K and row stride multiples of 8");
+  TORCH_CHECK(N <= INT32_MAX && K <= INT32_MAX, name, "dims");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-              "gemv_fused: 16-byte alignment");
+              name, "16-byte alignment");
   TORCH_CHECK(sumsq.scalar_type() == at::kLong && sumsq.numel() % 2 == 0 && sumsq.numel() / 2 >= M * 64 &&
                   (slot == 0 || slot == 1),
-              "gemv_fused: sumsq int64 [2, >= M, 64], slot 0 / 1");
+              name, "sumsq int64 [2, >= M, 64], slot 0 / 1");
   auto* acc = reinterpret_cast<unsigned long long*>(sumsq.data_ptr<int64_t>());
   const int64_t stride = sumsq.numel() / 2;
   grt::GemvFused f{};
@@ -1532,24 +1539,24 @@ Tensor gemv_fused(const Tensor& x, const Tensor& w, const Tensor& sumsq, int64_t
   const bool resnorm = res.has_value() && res->defined();
   const bool rope = cos.has_value() && cos->defined();
   TORCH_CHECK(!(normx && resnorm) && (normx || resnorm || rope),
-              "gemv_fused: g (normalise the input) or res (residual epilogue), and / or cos (RoPE epilogue)");
-  TORCH_CHECK(!(rope && (resnorm || swiglu)), "gemv_fused: the RoPE epilogue is for the qkv projection");
+              name, "g (normalise the input) or res (residual epilogue), and / or cos (RoPE epilogue)");
+  TORCH_CHECK(!(rope && (resnorm || swiglu)), name, "the RoPE epilogue is for the qkv projection");
   Tensor q;
   if (rope) {
-    TORCH_CHECK(sin.has_value() && pos.has_value() && kc.has_value() && vc.has_value(), "gemv_fused: rope needs sin / pos / kc / vc");
+    TORCH_CHECK(sin.has_value() && pos.has_value() && kc.has_value() && vc.has_value(), name, "rope needs sin / pos / kc / vc");
     // the head dim is the table's: cos / sin rows hold D / 2 angles
     TORCH_CHECK(cos->dim() >= 1 && (cos->size(-1) == 64 || cos->size(-1) == 32),
-                "gemv_fused: rope head_dim (2 * cos.size(-1)) must be 128 or 64");
+                name, "rope head_dim (2 * cos.size(-1)) must be 128 or 64");
     const int64_t D = 2 * cos->size(-1);
     check_rope(*cos, *sin, *pos, M, cos->numel() / (D / 2), D);
-    TORCH_CHECK(hq > 0 && hkv > 0 && N == (hq + 2 * hkv) * D, "gemv_fused: rope N == (hq + 2 hkv) * head_dim (", D, ")");
+    TORCH_CHECK(hq > 0 && hkv > 0 && N == (hq + 2 * hkv) * D, name, "rope N == (hq + 2 hkv) * head_dim (", D, ")");
     for (const Tensor* c : {&*kc, &*vc}) {
       check_cuda(*c, "cache");
       TORCH_CHECK(c->dim() == 4 && c->size(0) == M && c->size(2) == hkv && c->size(3) == D && c->stride(3) == 1 &&
                       c->scalar_type() == at::kBFloat16,
-                  "gemv_fused: cache bf16 [M, L, hkv, head_dim]");
+                  name, "cache bf16 [M, L, hkv, head_dim]");
     }
-    TORCH_CHECK(vc->sizes() == kc->sizes(), "gemv_fused: kc / vc shapes");
+    TORCH_CHECK(vc->sizes() == kc->sizes(), name, "kc / vc shapes");
     q = at::empty({M, hq, D}, x.options());
     f.q_out = q.data_ptr(), f.kc = kc->data_ptr(), f.vc = vc->data_ptr();
     f.c_bs = kc->stride(0), f.c_ss = kc->stride(1), f.c_hs = kc->stride(2);
@@ -1559,23 +1566,40 @@ Tensor gemv_fused(const Tensor& x, const Tensor& w, const Tensor& sumsq, int64_t
     f.head_dim = (int)D;
   }
   if (normx) {
-    TORCH_CHECK(!swiglu, "gemv_fused: normx and swiglu are exclusive");
+    TORCH_CHECK(!swiglu, name, "normx and swiglu are exclusive");
     check_contig(*g, "g");
     TORCH_CHECK(g->scalar_type() == at::kBFloat16 && g->numel() == K && reinterpret_cast<uintptr_t>(g->data_ptr()) % 16 == 0,
-                "gemv_fused: g bf16 [K], 16-byte aligned");
+                name, "g bf16 [K], 16-byte aligned");
     f.g = g->data_ptr(), f.sumsq_in = acc + slot * stride;
   } else if (resnorm) {
     check_cuda(*res, "res");
     TORCH_CHECK(res->dim() == 2 && res->size(0) == M && res->size(1) == N && res->stride(1) == 1 &&
-                    res->scalar_type() == at::kBFloat16, "gemv_fused: res bf16 [M, N]");
+                    res->scalar_type() == at::kBFloat16, name, "res bf16 [M, N]");
     f.res = res->data_ptr(), f.ldr = res->stride(0);
     f.sumsq_out = acc + slot * stride, f.sumsq_zero = acc + (1 - slot) * stride;
   }
   c10::OptionalDeviceGuard dg(x.device());
   Tensor y = rope ? q : at::empty({M, N}, x.options());
   f.y = rope ? nullptr : y.data_ptr(), f.ldy = N;
-  grt::gemv_fused_bf16(f, cur_stream(x));
+  if (mfma) grt::gemv_mfma_fused_bf16(f, cur_stream(x));
+  else grt::gemv_fused_bf16(f, cur_stream(x));
   return y;
+}
+
+Tensor gemv_fused(const Tensor& x, const Tensor& w, const Tensor& sumsq, int64_t slot, bool swiglu,
+                  const c10::optional<Tensor>& g, const c10::optional<Tensor>& res, double eps,
+                  const c10::optional<Tensor>& cos, const c10::optional<Tensor>& sin, const c10::optional<Tensor>& pos,
+                  const c10::optional<Tensor>& kc, const c10::optional<Tensor>& vc, int64_t hq, int64_t hkv) {
+  return gemv_fused_impl("gemv_fused: ", false, x, w, sumsq, slot, swiglu, g, res, eps, cos, sin, pos, kc, vc, hq, hkv);
+}
+
+Tensor gemv_mfma_fused(const Tensor& x, const Tensor& w, const Tensor& sumsq, int64_t slot, bool swiglu,
+                       const c10::optional<Tensor>& g, const c10::optional<Tensor>& res, double eps,
+                       const c10::optional<Tensor>& cos, const c10::optional<Tensor>& sin,
+                       const c10::optional<Tensor>& pos, const c10::optional<Tensor>& kc,
+                       const c10::optional<Tensor>& vc, int64_t hq, int64_t hkv) {
+  return gemv_fused_impl("gemv_mfma_fused: ", true, x, w, sumsq, slot, swiglu, g, res, eps, cos, sin, pos, kc, vc, hq,
+                         hkv);
 }
 
 // One token per row of logits [B, V] (sample.hip): greedy argmax, or (do_sample) a Gumbel-max draw
@@ -2148,6 +2172,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sdma_clear_error", [](int64_t device) { grt::sdma_clear_error((int)device); });
   m.def("gemv", &gemv, py::arg("x"), py::arg("w"), py::arg("swiglu") = false);
   m.def("gemv_fused", &gemv_fused, py::arg("x"), py::arg("w"), py::arg("sumsq"), py::arg("slot"),
+        py::arg("swiglu") = false, py::arg("g") = py::none(), py::arg("res") = py::none(), py::arg("eps") = 1e-5,
+        py::arg("cos") = py::none(), py::arg("sin") = py::none(), py::arg("pos") = py::none(),
+        py::arg("kc") = py::none(), py::arg("vc") = py::none(), py::arg("hq") = 0, py::arg("hkv") = 0);
+  m.def("gemv_mfma_fused", &gemv_mfma_fused, py::arg("x"), py::arg("w"), py::arg("sumsq"), py::arg("slot"),
         py::arg("swiglu") = false, py::arg("g") = py::none(), py::arg("res") = py::none(), py::arg("eps") = 1e-5,
         py::arg("cos") = py::none(), py::arg("sin") = py::none(), py::arg("pos") = py::none(),
         py::arg("kc") = py::none(), py::arg("vc") = py::none(), py::arg("hq") = 0, py::arg("hkv") = 0);

@@ -435,6 +435,10 @@ struct GemvFused {
   int rope_S, cache_L, hq, hkv, head_dim;
 };
 void gemv_fused_bf16(const GemvFused& f, hipStream_t s);
+// The same contracts for 3 <= M <= 16 rows on the MFMA skinny kernel (gemv_mfma_ok(M, K): K % 256
+// == 0; sumsq_in / sumsq_out / sumsq_zero hold M rows of 64 slots). One of sumsq_in, res, q_out is
+// set; sumsq_in and res are exclusive, as are q_out and res / swiglu.
+void gemv_mfma_fused_bf16(const GemvFused& f, hipStream_t s);
 int gemv_workgroups(int N);
 
 // ---------------- decode GEMV from NF4 codes (gemv_nf4.hip) ----------------

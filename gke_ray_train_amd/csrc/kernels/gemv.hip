@@ -26,8 +26,8 @@
 // projection: every workgroup re-read row, residual and weight from L2) and a last-workgroup
 // reduction behind a device-scope counter (+22-30 us: the release / acquire fences write back and
 // invalidate the whole L2 in every workgroup).
-#include "grt_common.h"
-#include "grt_kernels.h"
+// gemv_mfma_fused.hip holds the same prologues / epilogues on the MFMA skinny kernel (3-16 rows).
+#include "grt_gemv.h"  // PRO_* / EPI_*, GemvArgs, the accumulator layout
 
 namespace grt {
 namespace {
@@ -37,43 +37,6 @@ constexpr int kR = 4;  // weight rows per wave
 // lm_head 165 -> 149 us (7.1 TB/s), the small projections as before (tools/gemv_bench.py,
 // profiles/r5_decode.md)
 constexpr int kKS = 4;
-
-__device__ __forceinline__ float silu_f(float g) { return g / (1.f + __expf(-g)); }
-
-// input transform of x
-enum { PRO_NONE = 0, PRO_SWI = 1, PRO_NORMX = 2 };
-// output
-enum { EPI_NONE = 0, EPI_RESNORM = 1, EPI_ROPE = 2 };
-
-constexpr float kSumsqScale = 1048576.f;  // 2^20: fixed-point units of the sum-of-squares accumulator
-constexpr int kSumsqSlots = 64;           // accumulator addresses per row: workgroup b adds into b % 64
-
-struct GemvArgs {
-  const bf16* x;
-  int64_t ldx;
-  const bf16* w;
-  bf16* y;  // EPI_RESNORM: h = y + res
-  int64_t ldy;
-  int N, K;
-  const bf16* g;  // PRO_NORMX: norm weight [K]
-  float eps;      // PRO_NORMX
-  const unsigned long long* sumsq_in;  // PRO_NORMX: [M][kSumsqSlots] fixed-point partial sums of h^2
-  // EPI_RESNORM
-  const bf16* res;  // [M, N], row stride ldr
-  int64_t ldr;
-  unsigned long long* sumsq_out;   // [M][kSumsqSlots], zero at launch
-  unsigned long long* sumsq_zero;  // [M][kSumsqSlots], zeroed here for the next producer
-  // EPI_ROPE (the qkv projection, head_dim HD = 128 or 64): q rotated into q_out [M, hq, HD], k
-  // rotated and v written at cache slot pos[m] of kc / vc (row m = batch row m)
-  bf16* q_out;
-  bf16* kc;
-  bf16* vc;
-  int64_t c_bs, c_ss, c_hs, v_bs, v_ss, v_hs;
-  const float* cosb;  // [>= rope_S, HD / 2]
-  const float* sinb;
-  const int* pos;     // [M]
-  int rope_S, cache_L, hq, hkv;
-};
 
 // KS waves of the workgroup split K for the same kR rows (KS = 4: 4x the workgroups and weight
 // bytes in flight on the small projections, whose 1-workgroup-per-CU grid left HBM latency
@@ -266,7 +229,6 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
 // K step is one v_mfma_f32_16x16x32_bf16: A = the x rows (rows >= M read as zero), B = 16 weight
 // rows x 8 consecutive k per lane (16-byte non-temporal loads, kU steps in flight per lane). The
 // KS partial 16x16 tiles merge through LDS. K % (32 kU) == 0.
-constexpr int kU = 8;  // 32-wide K steps per wave per iteration
 template <int KS>
 __global__ __launch_bounds__(64 * KS) void gemv_mfma_kernel(const bf16* __restrict__ x, int64_t ldx,
                                                            const bf16* __restrict__ w, bf16* __restrict__ y,
@@ -349,15 +311,7 @@ void gemv_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, 
 }
 
 void gemv_fused_bf16(const GemvFused& f, hipStream_t s) {
-  GemvArgs a{};
-  a.x = static_cast<const bf16*>(f.x), a.ldx = f.ldx, a.w = static_cast<const bf16*>(f.w);
-  a.y = static_cast<bf16*>(f.y), a.ldy = f.ldy, a.N = f.N, a.K = f.K;
-  a.g = static_cast<const bf16*>(f.g), a.eps = f.eps, a.sumsq_in = f.sumsq_in;
-  a.res = static_cast<const bf16*>(f.res), a.ldr = f.ldr, a.sumsq_out = f.sumsq_out, a.sumsq_zero = f.sumsq_zero;
-  a.q_out = static_cast<bf16*>(f.q_out), a.kc = static_cast<bf16*>(f.kc), a.vc = static_cast<bf16*>(f.vc);
-  a.c_bs = f.c_bs, a.c_ss = f.c_ss, a.c_hs = f.c_hs, a.v_bs = f.v_bs, a.v_ss = f.v_ss, a.v_hs = f.v_hs;
-  a.cosb = f.cosb, a.sinb = f.sinb, a.pos = f.pos, a.rope_S = f.rope_S, a.cache_L = f.cache_L;
-  a.hq = f.hq, a.hkv = f.hkv;
+  const GemvArgs a = gemv_args(f);
   const bool normx = f.sumsq_in != nullptr, resnorm = f.res != nullptr, rope = f.q_out != nullptr;
   const bool d64 = f.head_dim == 64;  // the binding admits 128 or 64
   if (rope && normx && d64) launch_gemv<PRO_NORMX, EPI_ROPE, 64>(a, f.M, s);

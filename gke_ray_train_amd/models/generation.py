@@ -22,6 +22,17 @@ at its own last token, and row b then decodes at position len_b + t into cache s
 (over the K / V the prefill left there for the filler behind a short row) with len_b + t + 1 valid
 keys. No kernel knows about padding.
 
+When every projection is a plain bf16 ``Linear`` the captured step is the NORM-FUSED one: 5 launches
+per layer (qkv, attention, o_proj, gate_up, down_proj), with the residual adds, both RMSNorms, RoPE,
+the KV-cache append and SwiGLU inside the GEMVs (``_fused_norm_layer_step``). 1-2 rows run it on the
+FMA GEMV (``gemv_fused``); 3 to ``GEMV_MFMA_FUSED_MAX_ROWS`` rows, i.e. batched ``generate()``, on
+the MFMA skinny GEMM with the same prologues / epilogues (``gemv_mfma_fused``), which needs every
+projection's K to be a multiple of 256. That limit is 2, so no batch takes it: measured on the 8B
+and 1B geometries the step is 23-38 % slower than the generic one at 3-16 rows
+(profiles/decode_batch_fused.md). Anything else takes the generic step (8-9 launches per layer).
+The speculative verify step stays generic: its rows are T tokens of one sequence, so the RoPE
+epilogue would need a tokens-per-row term to find the cache row.
+
 With a sampler the step ends in ``sample_logits`` (csrc/kernels/sample.hip): greedy argmax or a
 temperature / top-k / top-p draw with counter-based noise, plus the loop's bookkeeping (pad after
 EOS, finished flags, the next step's input id, the output column), so ``generate()`` is
@@ -420,13 +431,27 @@ def _plain_bf16_linear(lin) -> bool:
 
 
 GEMV_FUSED_MAX_ROWS = 4  # gemv_fused's row limit (TORCH_CHECK in csrc/bindings/ops.cpp)
+# Rows up to which the norm-fused step runs on gemv_mfma_fused (the kernel takes 16): the largest
+# batch at which it beats the generic step by more than the round-to-round spread on the
+# Llama-3.1-8B geometry. As measured it is behind at every batch from 3 to 16 (5.70 against 4.28 ms
+# per step at 3 rows, spread under 0.2 %: every workgroup recomputes the SwiGLU / norm of its A
+# fragments; profiles/decode_batch_fused.md), so it admits no such batch.
+GEMV_MFMA_FUSED_MAX_ROWS = 2
+
+
+def _mfma_rows(rows: int) -> bool:
+    """Row counts of the norm-fused step that run on ``gemv_mfma_fused`` (the FMA ``gemv_fused`` below)."""
+    from ..ops import linear as _lin
+    return rows > min(_lin.GEMV_MAX_ROWS, GEMV_FUSED_MAX_ROWS)
 
 
 def _norm_fusable(model, B: int) -> bool:
-    """Every projection a plain bf16 Linear (no LoRA / NF4 wrappers, no bias) and 1-2 rows: the
-    decode step can run with its residual adds / RMSNorms inside the GEMVs (gemv.hip)."""
+    """Every projection a plain bf16 Linear (no LoRA / NF4 wrappers, no bias) and 1-2 rows, or 3 to
+    ``GEMV_MFMA_FUSED_MAX_ROWS`` rows with every projection's K a multiple of 256 (the MFMA skinny
+    kernel's K rule): the decode step can run with its residual adds / RMSNorms inside the GEMVs
+    (gemv.hip)."""
     from ..ops import linear as _lin
-    if not (_GEMV_NORM and _lin._GEMV and B <= min(_lin.GEMV_MAX_ROWS, GEMV_FUSED_MAX_ROWS) and _native.kernels_available()):
+    if not (_GEMV_NORM and _lin._GEMV and _native.kernels_available()):
         return False
     m = model.model
     norms = [m.norm] + [n for ly in m.layers for n in (ly.input_layernorm, ly.post_attention_layernorm)]
@@ -434,6 +459,10 @@ def _norm_fusable(model, B: int) -> bool:
                                                                ly.mlp.gate_up_proj, ly.mlp.down_proj)]
     if model.config.head_dim not in (64, 128):  # the RoPE epilogue / decode attention kernels
         return False
+    if _mfma_rows(B):  # gemv_mfma_fused: 3..16 rows (the kernel's tile), K % 256 == 0
+        k_ok = all(getattr(p, "in_features", 1) % 256 == 0 for p in lins)
+        if not (3 <= B <= min(GEMV_MFMA_FUSED_MAX_ROWS, 16) and k_ok):
+            return False
     return (all(_plain_bf16_linear(p) for p in lins)
             and all(n.weight.dtype == torch.bfloat16 and n.weight.is_contiguous() and n.weight.data_ptr() % 16 == 0
                     for n in norms))
@@ -456,8 +485,11 @@ def _fused_norm_layer_step(layer, h, first: bool, ws: _NormWorkspace, B, cos, si
     rotates q / k and appends k / v to the cache. ``h`` IS the residual stream between
     layers; slot 0 carries the post-attention norm's statistics, slot 1 the next input norm's.
     With an fp8 cache the qkv GEMV has no epilogue (its norm-on-load stays) and ``rope_append_fp8``
-    follows it, one more launch per layer; the fp8 decode kernel then reads the cache."""
+    follows it, one more launch per layer; the fp8 decode kernel then reads the cache.
+    1-2 rows run the FMA kernel (``gemv_fused``), more rows the MFMA skinny kernel
+    (``gemv_mfma_fused``): the same calls, contracts and launch list."""
     K = _native.kernels()
+    gemv_fused = K.gemv_mfma_fused if _mfma_rows(B) else K.gemv_fused
     attn, mlp = layer.self_attn, layer.mlp
     ln1, ln2 = layer.input_layernorm, layer.post_attention_layernorm
     hq, hkv, D = attn.hq, attn.hkv, attn.hd
@@ -466,18 +498,18 @@ def _fused_norm_layer_step(layer, h, first: bool, ws: _NormWorkspace, B, cos, si
     if first and cache.fp8:  # no norm-on-load and no epilogue: the plain GEMV
         q = K.gemv(ops.rms_norm(h, ln1.weight, ln1.eps), attn.qkv_proj.weight)
     elif first:  # layer 0: h is the embedding (no residual add, no producer GEMV summed its squares)
-        q = K.gemv_fused(ops.rms_norm(h, ln1.weight, ln1.eps), attn.qkv_proj.weight, ws.sumsq, 1, **rope)
+        q = gemv_fused(ops.rms_norm(h, ln1.weight, ln1.eps), attn.qkv_proj.weight, ws.sumsq, 1, **rope)
     else:
-        q = K.gemv_fused(h, attn.qkv_proj.weight, ws.sumsq, 1, g=ln1.weight, eps=ln1.eps, **rope)
+        q = gemv_fused(h, attn.qkv_proj.weight, ws.sumsq, 1, g=ln1.weight, eps=ln1.eps, **rope)
     if cache.fp8:  # q is the whole qkv row here
         q = _fp8_append(K, q, cos, sin, pos_b, hq, hkv, D, cache, li, 1)
         o = ops.decode_attention_fp8(q.view(B, 1, hq, D), cache.k[li], cache.v[li], cache.k_scale[li],
                                      cache.v_scale[li], seqlens_k=lens)
     else:
         o = ops.flash_attention(q.view(B, 1, hq, D), cache.k[li], cache.v[li], causal=False, seqlens_k=lens)
-    h = K.gemv_fused(o.reshape(B, hq * D), attn.o_proj.weight, ws.sumsq, 0, res=h)
-    gu = K.gemv_fused(h, mlp.gate_up_proj.weight, ws.sumsq, 0, g=ln2.weight, eps=ln2.eps)
-    return K.gemv_fused(gu, mlp.down_proj.weight, ws.sumsq, 1, swiglu=True, res=h)
+    h = gemv_fused(o.reshape(B, hq * D), attn.o_proj.weight, ws.sumsq, 0, res=h)
+    gu = gemv_fused(h, mlp.gate_up_proj.weight, ws.sumsq, 0, g=ln2.weight, eps=ln2.eps)
+    return gemv_fused(gu, mlp.down_proj.weight, ws.sumsq, 1, swiglu=True, res=h)
 
 
 _DEVICE_SAMPLER = os.environ.get("GRT_DEVICE_SAMPLER", "1") != "0"
@@ -675,8 +707,9 @@ class GraphDecoder:
                 h = _fused_norm_layer_step(layer, h, li == 0, self.norm_ws, B, self.cos, self.sin,
                                            self.cache, li, self.pos_b, self.lens)
             fn = m.model.norm
-            logits = _native.kernels().gemv_fused(h, m.lm_head.weight, self.norm_ws.sumsq, 1, g=fn.weight,
-                                                  eps=fn.eps)
+            K = _native.kernels()
+            logits = (K.gemv_mfma_fused if _mfma_rows(B) else K.gemv_fused)(
+                h, m.lm_head.weight, self.norm_ws.sumsq, 1, g=fn.weight, eps=fn.eps)
         else:
             with decode_step(B * T):  # warm-up and capture; a replay runs what was captured
                 logits = m.lm_head(_layers(m, h, lambda li, attn, qkv: _device_attention(

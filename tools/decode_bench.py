@@ -22,7 +22,10 @@ one-token kernel (``attn_main``).
 ``DECODE_KV=fp8`` times the fp8 KV cache (``generate(..., kv_cache_dtype="fp8")``) against the bf16
 cache, device loop, ``DECODE_B`` sequences with a prompt of ``DECODE_PROMPT`` (512) tokens
 (``kv_main``); with ``DECODE_ATTN=1`` it times the decode attention kernel alone over an fp8 and a
-bf16 cache instead (``kv_attn_main``)."""
+bf16 cache instead (``kv_attn_main``).
+
+``DECODE_FUSED=1`` times the norm-fused captured step at 3-16 sequences (``gemv_mfma_fused``) against
+the generic step (``fused_main``)."""
 import json
 import os
 import sys
@@ -297,6 +300,61 @@ def kv_attn_main():
                                       "time_ratio": round(us_f / us_b, 3)}), flush=True)
 
 
+def fused_main():
+    """``DECODE_FUSED=1``: the norm-fused captured step on ``gemv_mfma_fused`` against the generic step
+    at ``DECODE_B`` (a comma list, default 3,4,8,12,16) sequences, greedy, prompt ``DECODE_PROMPT``
+    (512), ``DECODE_NEW`` (64) tokens, device loop. ``generation._GEMV_NORM`` switches the arm; the
+    row limit is lifted to the kernel's 16 so that every batch has a fused arm. The arms alternate
+    ``DECODE_ROUNDS`` (2) times in this one process, the replays timed on their own with events as in
+    ``kv_main``. ``extension_calls_per_step`` counts the extension's calls of one step body: the layers'
+    and the step's own (layer 0's norm, LM head, sampler); library GEMMs are not among them."""
+    from gke_ray_train_amd import _native
+    from gke_ray_train_amd.models import generation as G
+    new = int(os.environ.get("DECODE_NEW", "64"))
+    P = int(os.environ.get("DECODE_PROMPT", "512"))
+    net = build_llama(model, device="cuda", dtype=torch.bfloat16, seed=0).eval()
+    n_layers = net.config.num_hidden_layers
+    G.GEMV_MFMA_FUSED_MAX_ROWS = 16
+    real, calls = _native.kernels(), []
+
+    class Counting:
+        def __getattr__(self, name):
+            fn = getattr(real, name)
+            if not callable(fn) or name.isupper():
+                return fn
+            return lambda *a, **k: (calls.append(name), fn(*a, **k))[1]
+
+    for B in [int(b) for b in os.environ.get("DECODE_B", "3,4,8,12,16").split(",")]:
+        ids = torch.randint(0, net.config.vocab_size, (B, P), device="cuda")
+        for rnd in range(int(os.environ.get("DECODE_ROUNDS", "2"))):
+            for fused in (True, False):
+                G._GEMV_NORM = fused
+                dec = G.GraphDecoder(net, B, P + new, sampler=G.SamplerConfig(max_new_tokens=new))
+                assert (dec.norm_ws is not None) == fused
+                dec.first_token(dec.prefill(ids))
+                _native.kernels, calls[:] = (lambda: Counting()), []
+                dec.advance()  # warm-up step body + captured step body
+                _native.kernels = lambda: real
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(new - 2):
+                    dec.advance()
+                b.record()
+                torch.cuda.synchronize()
+                step = a.elapsed_time(b) / (new - 2)  # ms per replay
+                print(json.dumps({"model": model, "step": "norm_fused" if fused else "generic", "batch": B,
+                                  "prompt": P, "round": rnd, "new_tokens": dec.n_emitted,
+                                  "extension_calls_per_step": len(calls) // 2, "layers": n_layers,
+                                  "ms_per_step": round(step, 3),
+                                  "decode_tokens_per_s": round(B / step * 1e3, 1)}), flush=True)
+                del dec
+                torch.cuda.empty_cache()
+    G._GEMV_NORM = True
+
+
+if "DECODE_FUSED" in os.environ:
+    fused_main()
+    sys.exit(0)
 if QUANT:
     nf4_main()
     sys.exit(0)

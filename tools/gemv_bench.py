@@ -97,6 +97,8 @@ def main():
     ap.add_argument("--flush", action="store_true",
                     help="evict the weights between calls (the decode step reads 16 GB between two uses)")
     ap.add_argument("--nf4", action="store_true", help="the NF4 GEMV on the quantised projection shapes")
+    ap.add_argument("--mfma-fused", action="store_true",
+                    help="time the fused prologues / epilogues on gemv_mfma_fused (--m 3-16) instead of gemv_fused")
     a = ap.parse_args()
     global FLUSH
     if a.flush:
@@ -123,21 +125,23 @@ def main():
         print(json.dumps({"shape": name, "N": N, "K": K, "m": a.m, "gemv_us": round(us, 1), "library_us": round(lib, 1),
                           "gemv_TBps": round(nb / us / 1e6, 2), "stream_read_us": round(ref, 1),
                           "stream_read_TBps": round(nb / ref / 1e6, 2)}), flush=True)
-        if name in NORM_INPUT and a.m <= 4:  # consumer of a norm: the input normalised on the fly (rstd, g)
+        # the FMA kernel's prologues / epilogues (1-4 rows), or with --mfma-fused the MFMA skinny kernel's (3-16)
+        gemv_fused, fused_rows = (C.gemv_mfma_fused, range(3, 17)) if a.mfma_fused else (C.gemv_fused, range(1, 5))
+        if name in NORM_INPUT and a.m in fused_rows:  # consumer of a norm: the input normalised on the fly (rstd, g)
             acc = torch.zeros(2, a.m, 64, dtype=torch.int64, device=dev)
             acc[:, :, 0] = K << 20
             g = torch.ones(K, device=dev, dtype=torch.bfloat16)
             r = torch.randn_like(x)
-            fused = med(lambda: C.gemv_fused(x, w, acc, 0, g=g), a.reps)
+            fused = med(lambda: gemv_fused(x, w, acc, 0, g=g), a.reps)
             sep = med(lambda: C.gemv(ops.add_rms_norm(x, r, g, 1e-5)[0], w), a.reps)
             extra_fused += (fused - us) * (32 if name != "lm_head" else 1)
             extra_sep += (sep - us) * (32 if name != "lm_head" else 1)
             print(json.dumps({"shape": name + "+norm", "fused_us": round(fused, 1),
                               "add_rms_norm_kernel_then_gemv_us": round(sep, 1)}), flush=True)
-        if name in NORM_PRODUCER and a.m <= 4:  # producer: + residual add and the next norm's rstd in the epilogue
+        if name in NORM_PRODUCER and a.m in fused_rows:  # producer: + residual add and the next norm's rstd in the epilogue
             r = torch.randn(a.m, N, device=dev, dtype=torch.bfloat16)
             acc = torch.zeros(2, a.m, 64, dtype=torch.int64, device=dev)
-            fused = med(lambda: C.gemv_fused(x, w, acc, 0, swiglu=swi, res=r), a.reps)
+            fused = med(lambda: gemv_fused(x, w, acc, 0, swiglu=swi, res=r), a.reps)
             extra_fused += (fused - us) * 32
             print(json.dumps({"shape": name + "+residual+rstd", "fused_us": round(fused, 1)}), flush=True)
         del w, x
