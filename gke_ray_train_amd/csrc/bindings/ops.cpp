@@ -694,6 +694,187 @@ void lora_refresh(const std::vector<Tensor>& bs, const std::vector<int64_t>& off
   grt::lora_refresh(p, cur_stream(w));
 }
 
+// ---- ranks 8 / 16 / 32 (lora_small.hip): the same contracts as the bindings above — false / {} for
+// a shape the kernels do not take, TORCH_CHECK for malformed arguments
+static bool lora_small_nt_fill(grt::LoraSmallNtParams& p, const std::vector<Tensor>& as, const std::vector<Tensor>& bts,
+                               const std::vector<Tensor>& cs) {
+  const int n = (int)as.size();
+  if (n < 1 || n > grt::kLoraGMax || (int)bts.size() != n || (int)cs.size() != n) return false;
+  const int64_t M = as[0].size(0);
+  const int r = (int)cs[0].size(1);
+  int kmin = INT_MAX;
+  for (int t = 0; t < n; ++t) {
+    const Tensor &a = as[t], &bt = bts[t], &c = cs[t];
+    if (!rowmajor_bf16(a) || !rowmajor_bf16(bt) || !rowmajor_bf16(c)) return false;
+    const int K = (int)a.size(1);
+    if (a.size(0) != M || c.size(0) != M || c.size(1) != r || bt.size(0) != r || bt.size(1) != K ||
+        !grt::lora_small_nt_supported(M, K, r) || c.get_device() != cs[0].get_device())
+      return false;
+    p.a[t] = a.data_ptr(); p.lda[t] = a.stride(0); p.bt[t] = bt.data_ptr(); p.ldbt[t] = bt.stride(0);
+    p.c[t] = c.data_ptr(); p.ldc[t] = c.stride(0); p.K[t] = K;
+    kmin = std::min(kmin, K);
+  }
+  for (int t = n; t < grt::kLoraGMax; ++t) {  // unused slots mirror product 0 (never indexed)
+    p.a[t] = p.a[0]; p.lda[t] = p.lda[0]; p.bt[t] = p.bt[0]; p.ldbt[t] = p.ldbt[0];
+    p.c[t] = p.c[0]; p.ldc[t] = p.ldc[0]; p.K[t] = p.K[0];
+  }
+  p.nprod = n; p.r = r; p.M = M;
+  p.ks = grt::lora_g_splits(M, kmin, device_cus(cs[0].get_device()), n);
+  return true;
+}
+
+// c_i [M, r] (+)= alpha * a_i [M, K_i] @ bt_i^T, bt_i = B_i^T [r, K_i], r in 8 .. 48 (lora_g_group's role)
+bool lora_small_g_group(const std::vector<Tensor>& as, const std::vector<Tensor>& bts, const std::vector<Tensor>& cs,
+                        double alpha, bool accumulate) {
+  grt::LoraSmallNtParams p{};
+  if (!lora_small_nt_fill(p, as, bts, cs)) return false;
+  const Tensor& c0 = cs[0];
+  c10::OptionalDeviceGuard dg(c0.device());
+  p.alpha = (float)alpha; p.accumulate = accumulate ? 1 : 0;
+  Tensor ws;
+  if (p.ks > 1) {
+    ws = at::empty({(int64_t)p.nprod * p.ks * p.M * p.r}, c0.options().dtype(at::kFloat));
+    p.ws = ws.data_ptr<float>();
+  }
+  grt::lora_small_nt(p, cur_stream(c0));
+  return true;
+}
+
+// lora_down's contract for R = r * targets in 8 .. 48 (R % 8 == 0): (h, xd) or {} when unsupported
+std::vector<Tensor> lora_small_down(const Tensor& x, const Tensor& a, double p, int64_t seed, int64_t offset,
+                                    bool want_xd, const optional<Tensor>& h_out, double hscale) {
+  check_cuda(x, "x");
+  check_contig(a, "a");
+  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && a.dim() == 2 && a.size(1) == x.size(1), "lora_small_down: shapes");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && a.scalar_type() == at::kBFloat16, "lora_small_down: bf16");
+  check_drop_p(p);
+  const int64_t M = x.size(0);
+  const int K = (int)x.size(1), R = (int)a.size(0);
+  if (offset % 4 != 0 || M < 1) return {};
+  c10::OptionalDeviceGuard g(x.device());
+  Tensor h;
+  if (h_out.has_value()) {
+    h = *h_out;
+    TORCH_CHECK(h.dim() == 2 && h.size(0) == M && h.size(1) == R && h.stride(1) == 1 && h.stride(0) % 8 == 0 &&
+                    h.scalar_type() == at::kBFloat16 && reinterpret_cast<uintptr_t>(h.data_ptr()) % 16 == 0,
+                "lora_small_down: h_out must be bf16 [M, R], unit column stride, 16-byte aligned rows");
+  } else {
+    h = at::empty({M, R}, x.options());
+  }
+  grt::LoraSmallNtParams lp{};
+  if (!lora_small_nt_fill(lp, {x}, {a}, {h})) return {};
+  Tensor xd;
+  if (want_xd) xd = at::empty({M, K}, x.options());
+  lp.alpha = (float)hscale; lp.accumulate = 0;
+  lp.xd = want_xd && p > 0 ? xd.data_ptr() : nullptr;
+  lp.p = (float)p; lp.seed = (uint64_t)seed; lp.offset = (uint64_t)offset;
+  Tensor ws;
+  if (lp.ks > 1) {
+    ws = at::empty({(int64_t)lp.ks * M * R}, x.options().dtype(at::kFloat));
+    lp.ws = ws.data_ptr<float>();
+  }
+  grt::lora_small_nt(lp, cur_stream(x));
+  if (want_xd && !(p > 0)) xd.copy_(x);  // no mask: x_d is x (callers pass want_xd only with p > 0)
+  if (want_xd) return {h, xd};
+  return {h};
+}
+
+// lora_tred / lora_tred_group for R in 8 .. 96 (R % 8 == 0) and any M
+static bool lora_small_tred_impl(const std::vector<Tensor>& as, const std::vector<Tensor>& hs,
+                                 const std::vector<Tensor>& outs, double alpha, const std::vector<bool>& accumulate,
+                                 bool transpose) {
+  const int n = (int)as.size();
+  if (n < 1 || n > grt::kLoraTredMax || (int)hs.size() != n || (int)outs.size() != n || (int)accumulate.size() != n ||
+      (transpose && n != 1))
+    return false;
+  const int64_t M = as[0].size(0);
+  const int R = (int)hs[0].size(1);
+  grt::LoraTredParams p{};
+  int nbt = 0;
+  for (int t = 0; t < n; ++t) {
+    const Tensor &a = as[t], &h = hs[t], &out = outs[t];
+    if (!rowmajor_bf16(a) || !rowmajor_bf16(h) || !rowmajor_bf16(out)) return false;
+    const int N = (int)a.size(1);
+    if (a.size(0) != M || h.size(0) != M || h.size(1) != R || !grt::lora_small_tred_supported(M, N, R)) return false;
+    if (transpose ? (out.size(0) != R || out.size(1) != N) : (out.size(0) != N || out.size(1) != R)) return false;
+    if (out.get_device() != outs[0].get_device()) return false;
+    p.a[t] = a.data_ptr(); p.lda[t] = a.stride(0); p.h[t] = h.data_ptr(); p.ldh[t] = h.stride(0);
+    p.out[t] = out.data_ptr(); p.ldo[t] = out.stride(0); p.N[t] = N; p.bo[t] = nbt;
+    p.accumulate[t] = accumulate[t] ? 1 : 0;
+    nbt += N / 128;
+  }
+  for (int t = n; t < grt::kLoraTredMax; ++t) {  // unused slots: never selected (bo past every block)
+    p.a[t] = p.a[0]; p.lda[t] = p.lda[0]; p.h[t] = p.h[0]; p.ldh[t] = p.ldh[0];
+    p.out[t] = p.out[0]; p.ldo[t] = p.ldo[0]; p.N[t] = p.N[0]; p.bo[t] = INT_MAX; p.accumulate[t] = 0;
+  }
+  const Tensor& o0 = outs[0];
+  c10::OptionalDeviceGuard dg(o0.device());
+  p.nprod = n; p.nbt = nbt; p.M = M; p.R = R;
+  p.ks = grt::lora_small_tred_splits(M, nbt * 128, device_cus(o0.get_device()));
+  Tensor ws = at::empty({(int64_t)p.ks * nbt * 128 * R}, o0.options().dtype(at::kFloat));
+  p.ws = ws.data_ptr<float>();
+  p.transpose = transpose ? 1 : 0; p.alpha = (float)alpha;
+  grt::lora_small_tred(p, cur_stream(o0));
+  return true;
+}
+
+bool lora_small_tred(const Tensor& a, const Tensor& h, const Tensor& out, double alpha, bool accumulate, bool transpose) {
+  return lora_small_tred_impl({a}, {h}, {out}, alpha, {accumulate}, transpose);
+}
+
+bool lora_small_tred_group(const std::vector<Tensor>& as, const std::vector<Tensor>& hs, const std::vector<Tensor>& outs,
+                           double alpha, const std::vector<bool>& accumulate) {
+  return lora_small_tred_impl(as, hs, outs, alpha, accumulate, false);
+}
+
+// lora_dx for R = 8 / 24: dx [M, K] (+)= keep / (1-p) * (g [M, R] @ at^T), at = A^T [K, R]
+bool lora_small_dx(const Tensor& g, const Tensor& at, const Tensor& dx, double p, int64_t seed, int64_t offset,
+                   bool accumulate) {
+  check_contig(at, "at");
+  TORCH_CHECK(g.dim() == 2 && at.dim() == 2 && dx.dim() == 2 && g.size(0) == dx.size(0) &&
+                  at.size(0) == dx.size(1) && at.size(1) == g.size(1), "lora_small_dx: shapes");
+  check_drop_p(p);
+  if (!rowmajor_bf16(g) || !rowmajor_bf16(dx) || !rowmajor_bf16(at) ||
+      !grt::lora_small_dx_supported(dx.size(0), (int)dx.size(1), (int)g.size(1), (uint64_t)offset))
+    return false;
+  c10::OptionalDeviceGuard dg(dx.device());
+  grt::LoraDxParams lp{};
+  lp.g = g.data_ptr(); lp.at = at.data_ptr(); lp.dx = dx.data_ptr();
+  lp.M = dx.size(0); lp.K = (int)dx.size(1); lp.R = (int)g.size(1);
+  lp.p = (float)p; lp.seed = (uint64_t)seed; lp.offset = (uint64_t)offset; lp.accumulate = accumulate ? 1 : 0;
+  lp.ldg = g.stride(0); lp.ld_out = dx.stride(0);
+  grt::lora_small_dx(lp, cur_stream(dx));
+  return true;
+}
+
+// lora_refresh for r in 8 .. 32 (r % 8 == 0): B_i [n_i, r] -> the tail of W' and (optional) the B^T buffer
+bool lora_small_refresh(const std::vector<Tensor>& bs, const std::vector<int64_t>& offs, Tensor& w,
+                        const optional<Tensor>& bt, int64_t col0) {
+  TORCH_CHECK(!bs.empty() && bs.size() <= 4 && offs.size() == bs.size(), "lora_small_refresh: 1-4 targets");
+  TORCH_CHECK(rowmajor_bf16(w) && col0 % 8 == 0 && (!bt.has_value() || rowmajor_bf16(*bt)),
+              "lora_small_refresh: bf16 W' (and B^T), 16-byte aligned rows");
+  grt::LoraRefreshParams p{};
+  p.ntarget = (int)bs.size();
+  p.r = (int)bs[0].size(1);
+  if (p.r % 8 != 0 || p.r < 8 || p.r > 32) return false;
+  for (size_t j = 0; j < bs.size(); ++j) {
+    check_contig(bs[j], "B");
+    TORCH_CHECK(bs[j].scalar_type() == at::kBFloat16 && bs[j].dim() == 2 && bs[j].size(1) == p.r &&
+                    bs[j].size(0) % 8 == 0 && offs[j] >= 0 && offs[j] % 8 == 0 && offs[j] + bs[j].size(0) <= w.size(0) &&
+                    col0 + (int64_t)(j + 1) * p.r <= w.size(1) &&
+                    reinterpret_cast<uintptr_t>(bs[j].data_ptr()) % 16 == 0 &&
+                    (!bt.has_value() || ((int64_t)(j + 1) * p.r <= bt->size(0) && offs[j] + bs[j].size(0) <= bt->size(1))),
+                "lora_small_refresh: B_i bf16 [n % 8 == 0, r] inside W'");
+    p.b[j] = bs[j].data_ptr(); p.off[j] = (int)offs[j]; p.n[j] = (int)bs[j].size(0);
+  }
+  p.w = w.data_ptr(); p.ldw = w.stride(0); p.col0 = (int)col0; p.trow0 = 0;
+  p.wt = bt.has_value() ? bt->data_ptr() : nullptr;
+  p.ldt = bt.has_value() ? bt->stride(0) : 0;
+  c10::OptionalDeviceGuard g(w.device());
+  grt::lora_small_refresh(p, cur_stream(w));
+  return true;
+}
+
 // ------------------------------------------------------------------ cross entropy
 std::vector<Tensor> ce_fwd(const Tensor& logits, const Tensor& labels, int64_t ignore_index) {
   check_cuda(logits, "logits");
@@ -2110,6 +2291,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("transpose"));
   m.def("lora_tred_group", &lora_tred_group, py::arg("a"), py::arg("h"), py::arg("out"), py::arg("alpha"),
         py::arg("accumulate"));
+  m.def("lora_small_g_group", &lora_small_g_group, py::arg("a"), py::arg("bt"), py::arg("c"), py::arg("alpha"),
+        py::arg("accumulate"));
+  m.def("lora_small_down", &lora_small_down, py::arg("x"), py::arg("a"), py::arg("p"), py::arg("seed"),
+        py::arg("offset"), py::arg("want_xd"), py::arg("h_out") = py::none(), py::arg("hscale") = 1.0);
+  m.def("lora_small_tred", &lora_small_tred, py::arg("a"), py::arg("h"), py::arg("out"), py::arg("alpha"),
+        py::arg("accumulate"), py::arg("transpose"));
+  m.def("lora_small_tred_group", &lora_small_tred_group, py::arg("a"), py::arg("h"), py::arg("out"), py::arg("alpha"),
+        py::arg("accumulate"));
+  m.def("lora_small_dx", &lora_small_dx, py::arg("g"), py::arg("at"), py::arg("dx"), py::arg("p"), py::arg("seed"),
+        py::arg("offset"), py::arg("accumulate"));
+  m.def("lora_small_refresh", &lora_small_refresh, py::arg("bs"), py::arg("offs"), py::arg("w"), py::arg("bt"),
+        py::arg("col0"));
   m.def("dropout_bwd_seeded", &dropout_bwd_seeded);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);

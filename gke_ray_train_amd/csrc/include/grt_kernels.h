@@ -197,6 +197,31 @@ bool lora_tred_supported(int64_t M, int N, int R);
 int lora_tred_splits(int64_t M, int N, int R, int cus);
 void lora_tred(const LoraTredParams& p, hipStream_t s);
 
+// ---------------- LoRA at ranks 8 / 16 / 32 (lora_small.hip) ----------------
+// C[M][r] (+)= alpha * A[M][K] B^T[r][K]^T on 16-wide rank tiles, r % 8 == 0, r <= 48. Serves the
+// adapter gradient g_i = s dY_i B_i (up to 4 products of the same M and r per launch) and, with one
+// product, the down-projection h' = hscale drop(x) A_cat^T: p > 0 applies the element-dropout mask of
+// lora_down to A's fragments; xd (optional, [M][K] contiguous) receives the masked operand.
+struct LoraSmallNtParams {
+  const void* a[kLoraGMax]; int64_t lda[kLoraGMax]; const void* bt[kLoraGMax]; int64_t ldbt[kLoraGMax];
+  void* c[kLoraGMax]; int64_t ldc[kLoraGMax]; int K[kLoraGMax];
+  int nprod = 1; int r;
+  int64_t M; float alpha; int accumulate;
+  int ks = 1; float* ws = nullptr;  // k splits through the fp32 workspace [nprod][ks][M][r]
+  void* xd = nullptr; float p = 0.f; uint64_t seed = 0; uint64_t offset = 0;
+};
+bool lora_small_nt_supported(int64_t M, int K, int r);
+void lora_small_nt(const LoraSmallNtParams& p, hipStream_t s);
+// lora_tred's products for R = 8 .. 96 (R % 8 == 0) and any M (the last token tile is masked)
+bool lora_small_tred_supported(int64_t M, int N, int R);
+int lora_small_tred_splits(int64_t M, int N, int cus);
+void lora_small_tred(const LoraTredParams& p, hipStream_t s);
+// lora_dx for R = 8 / 24 (R % 8 == 0, R <= 32; dx_in and gscale are not used)
+bool lora_small_dx_supported(int64_t M, int K, int R, uint64_t offset);
+void lora_small_dx(const LoraDxParams& p, hipStream_t s);
+// lora_refresh for r % 8 == 0, r <= 32
+void lora_small_refresh(const LoraRefreshParams& p, hipStream_t s);
+
 // ---------------- attention (attention.hip) ----------------
 struct AttnParams {
   const void* q; const void* k; const void* v; void* o; float* lse;

@@ -24,6 +24,8 @@ kernel). Then y = [x | h'] W'^T is ONE GEMM — base output plus every adapter's
 the per-target read-modify-writes of y disappear, for R extra K columns (1-5 % of the base GEMM
 at r = 64). The backward keeps the epilogue form (a single [dX | g] = dY W' GEMM was tried: its
 N = in + R runs ~15 % below the tiled N = in on hipBLASLt/rocBLAS, more than the g GEMMs it saves).
+Ranks: r % 64 == 0 runs lora.hip / lora_grad.hip, r = 8 / 16 / 32 runs lora_small.hip (the same form
+and the same direct-to-slot gradients); any other rank keeps the epilogue form on library GEMMs.
 
 Documented deviation: one dropout mask per fused input (HF draws separate masks for q, k, v).
 """
@@ -107,7 +109,7 @@ def _adapter_then_base_dx(ctx, C, base, dy2, g, acat):
     if not (_LORA_DX_EPI and _LORA_DX and g.is_cuda and g.dtype == acat.dtype == dy2.dtype == torch.bfloat16):
         return None
     t = torch.empty(g.shape[0], acat.shape[1], device=dy2.device, dtype=dy2.dtype)
-    if not C.lora_dx(g, acat.t().contiguous(), t, ctx.p, ctx.seed, ctx.offset, False):
+    if not _dx_kernel(C, g, acat.t().contiguous(), t, ctx, False):
         return None
     return _base_input_grad(base, dy2, t)
 
@@ -128,6 +130,10 @@ _NF4_STREAM_KCAT = os.environ.get("GRT_NF4_STREAM_KCAT", "1") != "0"
 # operand once) instead of hipBLASLt's skinny tiles (2-4 reads per product). GRT_LORA_GRAD_KERNELS=0:
 # library GEMMs.
 _LORA_GRAD_KERNELS = os.environ.get("GRT_LORA_GRAD_KERNELS", "1") != "0"
+# Ranks below 64 on the hot path: the K-concatenated forward and the one-pass kernels of
+# csrc/kernels/lora_small.hip (16-wide rank tiles; the same switches select the fall-backs). Any other
+# rank that is not a multiple of 64 keeps ``_LoraFn`` on library GEMMs.
+_SMALL_RANKS = (8, 16, 32)
 
 
 def _bf16_cuda(*ts):
@@ -135,8 +141,23 @@ def _bf16_cuda(*ts):
 
 
 def _tred_into(C, a, h, out, alpha, accumulate, transpose):
-    """out (+)= alpha a^T h on the one-pass token-reduction kernel; False when it does not apply."""
-    return _LORA_GRAD_KERNELS and _bf16_cuda(a, h, out) and C.lora_tred(a, h, out, alpha, accumulate, transpose)
+    """out (+)= alpha a^T h on the one-pass token-reduction kernel (lora_grad.hip at R % 64 == 0,
+    lora_small.hip at the other R <= 96); False when it does not apply."""
+    if not (_LORA_GRAD_KERNELS and _bf16_cuda(a, h, out)):
+        return False
+    if h.shape[1] % 64 == 0:
+        return C.lora_tred(a, h, out, alpha, accumulate, transpose)
+    return C.lora_small_tred(a, h, out, alpha, accumulate, transpose)
+
+
+def _dx_kernel(C, g, at, dx, ctx, accumulate):
+    """dx (+)= drop'(g at^T) in one pass over dx: lora_dx (R % 16 == 0) or lora_small_dx (R = 8 / 24).
+    False when neither applies, which includes row strides off the kernels' 16-byte rows
+    (r % 8 != 0: the bindings reject those as malformed)."""
+    if g.stride(0) % 8 or dx.stride(0) % 8:
+        return False
+    fn = C.lora_dx if g.shape[1] % 16 == 0 else C.lora_small_dx
+    return fn(g, at, dx, ctx.p, ctx.seed, ctx.offset, accumulate)
 
 
 def _packed(ts):
@@ -186,7 +207,7 @@ def _lora_dx(ctx, C, base, dy2, g, acat):
     if dx is None:
         dx = _base_input_grad(base, dy2)                   # base dX (frozen weight)
         bf16 = g.dtype == acat.dtype == dx.dtype == torch.bfloat16
-        if not (_LORA_DX and bf16 and C.lora_dx(g, acat.t().contiguous(), dx, ctx.p, ctx.seed, ctx.offset, True)):
+        if not (_LORA_DX and bf16 and _dx_kernel(C, g, acat.t().contiguous(), dx, ctx, True)):
             if ctx.p > 0:
                 C.dropout_bwd_seeded(g @ acat, dx, ctx.p, ctx.seed, ctx.offset, True)
             else:
@@ -283,6 +304,8 @@ class _LoraKcatFn(torch.autograd.Function):
         pk = _packed(As)
         order, acat = (list(range(k)), torch.cat(As, 0)) if pk is None else pk
         res = C.lora_down(x, acat, p, seed, offset, p > 0, h_out=xw[:, K:], hscale=s) if _LORA_DOWN else []
+        if not res and _LORA_DOWN:  # R = 8 / 16 / 24 / 48: lora_small.hip (R % 32 == 0 stays on lora_down)
+            res = C.lora_small_down(x, acat, p, seed, offset, p > 0, h_out=xw[:, K:], hscale=s)
         if res:
             xd = res[1] if p > 0 else x
         else:
@@ -315,7 +338,8 @@ class _LoraKcatFn(torch.autograd.Function):
         bt = getattr(mod, "_bt", None) if _LORA_GRAD_KERNELS and _bf16_cuda(dy2, hc) else None
         # g_i = s dY_i B_i of every target in one launch (B_i^T: rows j r .. of the B^T buffer
         # lora_refresh filled in this step's forward)
-        g_done = bt is not None and C.lora_g_group(
+        g_group = C.lora_g_group if r % 64 == 0 else C.lora_small_g_group  # lora_grad.hip / lora_small.hip
+        g_done = bt is not None and g_group(
             [dy2[:, mod._spec[i][0]:mod._spec[i][0] + mod._spec[i][1]] for i in order],
             [bt[j * r:(j + 1) * r, mod._spec[i][0]:mod._spec[i][0] + mod._spec[i][1]] for j, i in enumerate(order)],
             [g[:, j * r:(j + 1) * r] for j in range(len(order))], s, False)
@@ -325,7 +349,7 @@ class _LoraKcatFn(torch.autograd.Function):
             slots = [_slot_of(Bs[i]) for i in order]
             outs = [sl.view if sl is not None else torch.empty(mod._spec[i][1], r, device=dy2.device, dtype=dy2.dtype)
                     for sl, i in zip(slots, order)]
-            db_done = C.lora_tred_group(
+            db_done = (C.lora_tred_group if r % 64 == 0 else C.lora_small_tred_group)(
                 [dy2[:, mod._spec[i][0]:mod._spec[i][0] + mod._spec[i][1]] for i in order],
                 [hc[:, j * r:(j + 1) * r] for j in range(len(order))], outs, 1.0,
                 [sl is not None and sl.accumulate for sl in slots])
@@ -339,7 +363,8 @@ class _LoraKcatFn(torch.autograd.Function):
             off, n, _ = mod._spec[i]
             dyi = dy2[:, off:off + n]
             gj = g[:, j * r:(j + 1) * r]
-            if not (g_done or (bt is not None and C.lora_g(dyi, bt[j * r:(j + 1) * r, off:off + n], gj, s, False))):
+            if not (g_done or (bt is not None and r % 64 == 0
+                               and C.lora_g(dyi, bt[j * r:(j + 1) * r, off:off + n], gj, s, False))):
                 gj.addmm_(dyi, Bs[i], beta=0.0, alpha=s)
             if not db_done:                                  # h' = s h: dB_i = dY_i^T h'_i
                 dBs[i] = _lora_dB(C, Bs[i], dyi, hc[:, j * r:(j + 1) * r], 1.0, kernels=True)
@@ -412,7 +437,7 @@ class LoraLinear(nn.Module):
         """R when the K-concatenated form applies (the producer then leaves R tail columns), else 0."""
         R = self.r * len(self.targets)
         b = self.base
-        if not (_LORA_KCAT and self.r % 64 == 0 and self.in_features % 128 == 0 and R <= 256
+        if not (_LORA_KCAT and (self.r % 64 == 0 or self.r in _SMALL_RANKS) and self.in_features % 128 == 0 and R <= 256
                 and all(n % 64 == 0 and off % 8 == 0 for _, off, n in self.targets)):
             return 0
         if isinstance(b, NF4Linear):
@@ -466,9 +491,13 @@ class LoraLinear(nn.Module):
         bl = [Bs[i].detach() for i in order]
         offs = [self._spec[i][0] for i in order]
         if all(b.is_contiguous() for b in bl):
-            if _LORA_GRAD_KERNELS and r == 64 and wk.is_cuda:
-                if self._bt is None:
-                    self._bt = torch.zeros(r * len(self.targets), self.out_features, device=wk.device, dtype=wk.dtype)
+            if _LORA_GRAD_KERNELS and (r == 64 or r in _SMALL_RANKS) and wk.is_cuda and self._bt is None:
+                self._bt = torch.zeros(r * len(self.targets), self.out_features, device=wk.device, dtype=wk.dtype)
+            if r in _SMALL_RANKS:  # lora_small.hip (lora_refresh works in 64-column slabs)
+                bt = self._bt if _LORA_GRAD_KERNELS and wk.is_cuda else None
+                if not _native.kernels().lora_small_refresh(bl, offs, wk, bt, K):
+                    raise RuntimeError(f"lora_small_refresh refused r = {r}")
+            elif _LORA_GRAD_KERNELS and r == 64 and wk.is_cuda:
                 _native.kernels().lora_refresh(bl, offs, wk, self._bt, K, 0)
             else:
                 _native.kernels().lora_refresh(bl, offs, wk, None, K)
