@@ -1791,12 +1791,17 @@ Tensor gemv_mfma_fused(const Tensor& x, const Tensor& w, const Tensor& sumsq, in
 // finished rows emit pad_id, the token goes to next_ids[b] and out[b, step[0]], and a row whose
 // winner is one of eos_ids gets finished[b] = true, finish_step[b] = step[0]. max_steps: the caller's
 // bound on step[0] + 1 (a step past out's last column writes no column).
+// Logits processors (sample.hip header): seen [B, ceil(V / 32) rounded up to 4] int32 / uint32 with
+// repetition_penalty != 1 penalises the tokens whose bit is set and sets the emitted token's bit
+// (penalty 1: seen is neither read nor written); min_p in (0, 1] (0: off) with do_sample; while
+// step[0] < min_new_tokens (state mode) the eos_ids count as -inf.
 Tensor sample_logits(const Tensor& logits, bool do_sample, double temperature, int64_t top_k, double top_p, int64_t seed,
                      const optional<Tensor>& counter, const optional<Tensor>& keep_mask,
                      const optional<Tensor>& finished, const optional<Tensor>& finish_step,
                      const optional<Tensor>& step, const optional<Tensor>& next_ids, const optional<Tensor>& out,
                      const optional<Tensor>& eos_ids, const optional<int64_t>& pad_id, int64_t max_steps,
-                     bool candidates) {
+                     bool candidates, const optional<Tensor>& seen, double repetition_penalty, double min_p,
+                     int64_t min_new_tokens) {
   check_cuda(logits, "logits");
   const grt::DType dt = dtype_of(logits);
   TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1, "sample_logits: logits [B, V], B, V >= 1");
@@ -1808,6 +1813,10 @@ Tensor sample_logits(const Tensor& logits, bool do_sample, double temperature, i
   TORCH_CHECK(temperature > 0.0 && std::isfinite(temperature), "sample_logits: temperature must be > 0, got ", temperature);
   TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "sample_logits: top_p must be in (0, 1], got ", top_p);
   TORCH_CHECK(top_k >= 0, "sample_logits: top_k must be >= 0, got ", top_k);
+  TORCH_CHECK(repetition_penalty > 0.0 && std::isfinite(repetition_penalty),
+              "sample_logits: repetition_penalty must be > 0, got ", repetition_penalty);
+  TORCH_CHECK(min_p >= 0.0 && min_p <= 1.0, "sample_logits: min_p must be in [0, 1], got ", min_p);
+  TORCH_CHECK(min_new_tokens >= 0, "sample_logits: min_new_tokens must be >= 0, got ", min_new_tokens);
   auto state_vec = [&](const optional<Tensor>& t, const char* name, int64_t n) -> int64_t* {
     check_contig(*t, name);
     TORCH_CHECK(t->scalar_type() == at::kLong && t->numel() == n && t->device() == logits.device(), "sample_logits: ", name,
@@ -1837,6 +1846,23 @@ Tensor sample_logits(const Tensor& logits, bool do_sample, double temperature, i
   TORCH_CHECK(state || (!given(eos_ids) && !pad_id.has_value()), "sample_logits: eos_ids / pad_id need the state tensors");
   TORCH_CHECK(!candidates || !state, "sample_logits: candidates mode takes no state tensors");
   a.candidates = candidates;
+  TORCH_CHECK(min_new_tokens == 0 || state, "sample_logits: min_new_tokens needs the state tensors (step)");
+  a.min_new = min_new_tokens;
+  a.min_p_on = do_sample && min_p > 0.0;
+  a.ln_min_p = a.min_p_on ? (float)std::log(min_p) : 0.f;  // ln in double, rounded once to fp32
+  a.penalty = (float)repetition_penalty;
+  TORCH_CHECK(a.penalty == 1.0f || given(seen), "sample_logits: repetition_penalty != 1 needs the seen bitmap");
+  if (given(seen) && a.penalty != 1.0f) {
+    TORCH_CHECK(!candidates, "sample_logits: candidates mode takes no repetition penalty");
+    const int64_t W = grt::seen_words(V);
+    TORCH_CHECK((seen->scalar_type() == at::kInt || seen->scalar_type() == at::kUInt32) && seen->dim() == 2 &&
+                    seen->size(0) == B && seen->size(1) == W && seen->stride(1) == 1 &&
+                    (B == 1 || (seen->stride(0) >= W && seen->stride(0) % 4 == 0)) && seen->device() == logits.device() &&
+                    reinterpret_cast<uintptr_t>(seen->data_ptr()) % 16 == 0,
+                "sample_logits: seen int32 / uint32 [B, ", W, "] (ceil(V / 32) rounded up to 4 words), 16-byte aligned "
+                "rows, on the logits' device");
+    a.seen = static_cast<uint32_t*>(seen->data_ptr()), a.seen_ld = B == 1 ? W : seen->stride(0);
+  }
   c10::OptionalDeviceGuard dg(logits.device());
   Tensor tokens;
   if (given(next_ids)) {
@@ -1871,6 +1897,37 @@ Tensor sample_logits(const Tensor& logits, bool do_sample, double temperature, i
   }
   grt::sample_logits(logits.data_ptr(), dt, a, cur_stream(logits));
   return tokens;
+}
+
+// Sets the bits of ids [B, S] (int64, last dimension contiguous) in the sampler's seen bitmap
+// [B, ceil(V / 32) rounded up to 4] (sample.hip): row b's ids[b, :lens[b]] (lens int32 [B]), or the
+// whole row without lens. Ids outside [0, V) set nothing; vocab_size = V, or -1 for every bit the
+// bitmap holds (32 per word).
+void seen_tokens_add(const Tensor& ids, const Tensor& seen, const optional<Tensor>& lens, int64_t vocab_size) {
+  check_cuda(ids, "ids");
+  check_cuda(seen, "seen");
+  TORCH_CHECK(ids.scalar_type() == at::kLong && ids.dim() == 2 && (ids.size(1) <= 1 || ids.stride(1) == 1),
+              "seen_tokens_add: ids int64 [B, S], last dimension contiguous");
+  TORCH_CHECK(seen.dim() == 2, "seen_tokens_add: seen [B, W]");
+  const int64_t B = ids.size(0), S = ids.size(1);
+  const int64_t V = vocab_size >= 0 ? vocab_size : std::min<int64_t>(seen.size(1) * 32, INT32_MAX);
+  TORCH_CHECK(V >= 1 && V <= INT32_MAX && B <= INT32_MAX, "seen_tokens_add: 1 <= vocab_size < 2^31, B < 2^31");
+  const int64_t W = grt::seen_words(V);
+  TORCH_CHECK((seen.scalar_type() == at::kInt || seen.scalar_type() == at::kUInt32) && seen.size(0) == B &&
+                  seen.size(1) == W && seen.stride(1) == 1 && (B <= 1 || seen.stride(0) >= W) &&
+                  seen.device() == ids.device(),
+              "seen_tokens_add: seen int32 / uint32 [B, ", W, "] on the ids' device");
+  const int32_t* lens_p = nullptr;
+  if (lens.has_value() && lens->defined()) {
+    check_contig(*lens, "lens");
+    TORCH_CHECK(lens->scalar_type() == at::kInt && lens->numel() == B && lens->device() == ids.device(),
+                "seen_tokens_add: lens int32 [B] on the ids' device");
+    lens_p = lens->data_ptr<int32_t>();
+  }
+  if (B == 0 || S == 0) return;
+  c10::OptionalDeviceGuard dg(ids.device());
+  grt::seen_tokens_add(ids.data_ptr<int64_t>(), B == 1 ? S : ids.stride(0), lens_p, (int)B, S, V,
+                       static_cast<uint32_t*>(seen.data_ptr()), B == 1 ? W : seen.stride(0), cur_stream(ids));
 }
 
 // Accept + draft step of speculative decoding (spec.hip), one sequence, K = drafts.numel() in 1..3.
@@ -2386,7 +2443,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keep_mask") = py::none(), py::arg("finished") = py::none(), py::arg("finish_step") = py::none(),
         py::arg("step") = py::none(), py::arg("next_ids") = py::none(), py::arg("out") = py::none(),
         py::arg("eos_ids") = py::none(), py::arg("pad_id") = py::none(), py::arg("max_steps") = 1,
-        py::arg("candidates") = false);
+        py::arg("candidates") = false, py::arg("seen") = py::none(), py::arg("repetition_penalty") = 1.0,
+        py::arg("min_p") = 0.0, py::arg("min_new_tokens") = 0);
+  m.def("seen_tokens_add", &seen_tokens_add, py::arg("ids"), py::arg("seen"), py::arg("lens") = py::none(),
+        py::arg("vocab_size") = -1);
   m.def("spec_advance", &spec_advance, py::arg("cand"), py::arg("drafts"), py::arg("ids"), py::arg("pos"),
         py::arg("lens"), py::arg("n_step"), py::arg("counter"), py::arg("finished"), py::arg("finish_step"),
         py::arg("done"), py::arg("out"), py::arg("hist"), py::arg("prompt_len"), py::arg("max_new"),

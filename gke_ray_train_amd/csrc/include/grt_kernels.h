@@ -543,8 +543,24 @@ struct SampleArgs {
   int64_t pad_id;
   int64_t* out;
   int64_t out_ld, out_cols;
+  // logits processors (sample.hip header). seen != null: repetition penalty `penalty` (!= 1) on the
+  // tokens whose bit is set in row b of the bitmap [B, seen_ld] (uint32 words, seen_ld a multiple of
+  // 4, 16-byte aligned rows); the emitted token's bit is set unless the row was finished.
+  uint32_t* seen;
+  int64_t seen_ld;
+  float penalty;
+  bool min_p_on;      // keep i iff z_i >= z_max + ln_min_p (sampling only)
+  float ln_min_p;     // fp32(ln(min_p)), <= 0
+  int64_t min_new;    // state mode: while step[0] < min_new the eos ids count as -inf
 };
 void sample_logits(const void* logits, DType dt, const SampleArgs& a, hipStream_t s);
+
+// Sets bit id & 31 of word seen[b][id >> 5] for every id = ids[b][s], s < (lens ? lens[b] : S), with
+// 0 <= id < V (other ids set nothing). ids [B, S] row stride ids_ld; seen [B, seen_ld] uint32.
+constexpr int kSeenLdsMaxV = 262144;  // vocabularies up to this stage the row's bitmap in LDS (32 KB)
+constexpr int64_t seen_words(int64_t V) { return ((V + 31) / 32 + 3) / 4 * 4; }
+void seen_tokens_add(const int64_t* ids, int64_t ids_ld, const int32_t* lens, int B, int64_t S, int64_t V,
+                     uint32_t* seen, int64_t seen_ld, hipStream_t s);
 
 // ---------------- speculative decoding: accept + draft (spec.hip) ----------------
 // One sequence. cand [K + 1] are the sampler's candidates of the verify step whose inputs were

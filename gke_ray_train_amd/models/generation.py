@@ -42,6 +42,14 @@ back-to-back replays with no torch op between them and one host read of ``finish
 the graph returns. ``ops/_ref.py::sample_tokens`` is the sampler's host implementation: the same
 logits, seed and counter give the same token on either device.
 
+Logits processors (``generate(..., repetition_penalty=, min_p=, min_new_tokens=)``, HF's names): all
+three run inside that sampler kernel. The repetition penalty reads a per-row bitmap of the tokens
+seen so far, which ``GraphDecoder`` owns: ``seen_tokens_add`` fills it from the prompt during the
+prefill, the kernel stages the row's words in LDS, penalises in every pass and sets the bit of the
+token it emits, so the captured step still needs no torch op. min_p is one more threshold of the
+kept set and min_new_tokens a per-element test against the EOS ids. The host loops apply
+``_ref.sample_process`` / ``sample_tokens``, the same fp32 operations, with a bool seen set.
+
 Prompt-lookup speculative decoding (``generate(..., prompt_lookup_num_tokens=K)``, one sequence)
 replaces the one-token step by a VERIFY step of T = K + 1 tokens: the last emitted token, not yet
 in the cache, and K drafts copied from where the last n-gram occurred before in the prompt and the
@@ -527,6 +535,40 @@ class SamplerConfig:
     seed: int = 0
     eos_ids: Tuple[int, ...] = ()
     pad_id: Optional[int] = None
+    repetition_penalty: float = 1.0  # 1.0: off; else the decoder owns a seen-token bitmap
+    min_p: float = 0.0               # 0.0: off
+    min_new_tokens: int = 0          # the EOS ids count as -inf for the first min_new_tokens tokens
+
+    @property
+    def processors(self) -> dict:
+        """The logits-processor arguments of ``_ref.sample_tokens`` that do not change per token."""
+        return dict(repetition_penalty=self.repetition_penalty, min_p=self.min_p)
+
+    def suppress(self, t: int) -> Tuple[int, ...]:
+        """The ids that count as -inf at token number ``t`` (``min_new_tokens``)."""
+        return self.eos_ids if t < self.min_new_tokens else ()
+
+
+def _check_processors(c: SamplerConfig) -> None:
+    if not c.repetition_penalty > 0.0:
+        raise ValueError(f"repetition_penalty must be > 0, got {c.repetition_penalty}")
+    if not 0.0 <= c.min_p <= 1.0:
+        raise ValueError(f"min_p must be in [0, 1], got {c.min_p}")
+    if not 0 <= c.min_new_tokens <= c.max_new_tokens:
+        raise ValueError(f"min_new_tokens must be in 0..max_new_tokens ({c.max_new_tokens}), got {c.min_new_tokens}")
+
+
+def _seen_prompt(input_ids: torch.Tensor, rows: Optional[_MaskRows], V: int) -> torch.Tensor:
+    """The host loop's seen set, bool [B, V] on the ids' device: row b's (masked) prompt tokens."""
+    B, S = input_ids.shape
+    seen = torch.zeros(B, V + 1, dtype=torch.bool, device=input_ids.device)  # column V takes what does not count
+    valid = (input_ids >= 0) & (input_ids < V)
+    if rows is not None:
+        j = torch.arange(S, device=input_ids.device)[None, :]
+        start = torch.tensor(rows.start, device=input_ids.device)[:, None]
+        lens = torch.tensor(rows.lens, device=input_ids.device)[:, None]
+        valid &= (j >= start) & (j < start + lens)
+    return seen.scatter_(1, torch.where(valid, input_ids, torch.full_like(input_ids, V)), True)[:, :V].contiguous()
 
 
 SPEC_MAX_DRAFTS = 3  # kSpecMaxDrafts (csrc/include/grt_kernels.h): K + 1 <= 4 rows, the GEMV family's limit
@@ -566,6 +608,12 @@ class GraphDecoder:
     ``kv_cache_dtype="fp8"`` stores the cache as e4m3fn codes (see module doc); every mode above
     takes it.
 
+    A sampler with ``repetition_penalty`` != 1 makes the decoder own ``seen``, the per-row bitmap of
+    the tokens in the prompt or emitted so far (int32 [B, ceil(V / 32) rounded up to 4], read as
+    uint32 words): ``prefill`` fills it with one ``seen_tokens_add`` call, and the
+    sampler reads it and sets the bit of the token it emits, inside the captured step. ``min_p`` and
+    ``min_new_tokens`` are arguments of the same sampler call. A ``SpecConfig`` takes ``min_p`` only.
+
     Needs a bf16 Llama on the GPU with head_dim 128 or 64 (the HIP RoPE epilogue / decode
     attention kernels)."""
 
@@ -599,11 +647,17 @@ class GraphDecoder:
         self.norm_ws = (_NormWorkspace(B, dev)
                         if dev.type == "cuda" and spec is None and _norm_fusable(model, B) else None)
         self.sampler = sampler
+        self.seen = None
         if sampler is not None:
             if len(sampler.eos_ids) > SAMPLER_MAX_EOS:
                 raise ValueError(f"the device sampler takes at most {SAMPLER_MAX_EOS} EOS ids, got {len(sampler.eos_ids)}")
             if sampler.max_new_tokens < 1:
                 raise ValueError("SamplerConfig.max_new_tokens must be >= 1")
+            _check_processors(sampler)
+            if spec is not None and (sampler.repetition_penalty != 1.0 or sampler.min_new_tokens > 0):
+                raise ValueError("speculative decoding takes no repetition_penalty / min_new_tokens")
+            if sampler.repetition_penalty != 1.0:
+                self.seen = torch.zeros(B, _ref.seen_words(model.config.vocab_size), dtype=torch.int32, device=dev)
             self.finished = torch.zeros(B, dtype=torch.bool, device=dev)
             self.finish_step = torch.full((B,), -1, dtype=torch.long, device=dev)
             self.n_step = torch.zeros(1, dtype=torch.long, device=dev)    # column of `out` the next token takes
@@ -633,7 +687,7 @@ class GraphDecoder:
             logits = logits.float()
         rows = logits.shape[0]  # 1 for the prefill logits: only cand[0] is read, no draft can match
         K.sample_logits(logits, do_sample=c.do_sample, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p,
-                        seed=c.seed, counter=self.counter, next_ids=self.cand[:rows], candidates=True)
+                        seed=c.seed, counter=self.counter, next_ids=self.cand[:rows], candidates=True, min_p=c.min_p)
         K.spec_advance(self.cand, self.drafts, self.ids.view(self.T), self.pos_b, self.lens, self.n_step, self.counter,
                        self.finished, self.finish_step, self.done, self.out.view(-1), self.hist, self.prompt_len,
                        c.max_new_tokens, self.spec.max_ngram, self.model.config.vocab_size, plan=self.spec.plan,
@@ -650,7 +704,8 @@ class GraphDecoder:
             logits, do_sample=c.do_sample, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p, seed=c.seed,
             counter=self.counter, finished=self.finished, finish_step=self.finish_step, step=self.n_step,
             next_ids=self.ids.view(self.B), out=self.out, eos_ids=self.eos_t, pad_id=c.pad_id,
-            max_steps=c.max_new_tokens)
+            max_steps=c.max_new_tokens, seen=self.seen, repetition_penalty=c.repetition_penalty, min_p=c.min_p,
+            min_new_tokens=c.min_new_tokens)
         self.counter.add_(1)
         self.n_step.add_(1)
 
@@ -670,6 +725,8 @@ class GraphDecoder:
         if self.spec is not None:
             return self._spec_prefill(input_ids, attention_mask, prefill_chunk_size)
         logits = _prefill(self.model, input_ids, self.cache, attention_mask, prefill_chunk_size)
+        if self.seen is not None:
+            self._seen_add(input_ids, attention_mask)
         n = self.cache.len
         if self.cache.lens is None:
             self.pos_b.fill_(n)
@@ -679,6 +736,16 @@ class GraphDecoder:
             self.lens.copy_(self.cache.lens + 1)
             self.cache.lens = self.pos_b  # the replays advance it
         return logits
+
+    def _seen_add(self, input_ids: torch.Tensor, attention_mask) -> None:
+        """The prompt's tokens into the seen bitmap: the compacted rows of a padded batch up to each
+        row's length, else every column."""
+        K, V = _native.kernels(), self.model.config.vocab_size
+        rows = _mask_rows(attention_mask, *input_ids.shape)
+        if rows is None:
+            return K.seen_tokens_add(input_ids, self.seen, vocab_size=V)
+        lens = torch.tensor(rows.lens, dtype=torch.int32, device=input_ids.device)
+        K.seen_tokens_add(_compact(input_ids, rows), self.seen, lens=lens, vocab_size=V)
 
     def _spec_prefill(self, input_ids: torch.Tensor, attention_mask=None, prefill_chunk_size=None) -> torch.Tensor:
         """Prefill of the one row (a padded row's tokens are compacted as in ``forward_cached``;
@@ -739,6 +806,8 @@ class GraphDecoder:
         if self.sampler is not None:  # the sampler's epilogue writes these; column n_step of `out`
             # is written again, with the same token, by the first replay
             state += [self.ids, self.finished, self.finish_step, self.n_step, self.counter]
+            if self.seen is not None:  # the warm-up and the capture run set the bits of the tokens they pick
+                state.append(self.seen)
             if self.spec is not None:  # out / hist past n_step are rewritten alike by the first replay
                 state += [self.drafts, self.done, self.cand]
         saved = [t.clone() for t in state]
@@ -861,7 +930,8 @@ def _spec_generate(model, input_ids, rows, P: int, sampler: SamplerConfig, spec:
         if not sampler.do_sample:
             return logits.argmax(-1).tolist()
         return [int(_ref.sample_tokens(logits[t:t + 1], seed=sampler.seed, counter=n + t, temperature=sampler.temperature,
-                                       top_k=sampler.top_k, top_p=sampler.top_p)) for t in range(logits.shape[0])]
+                                       top_k=sampler.top_k, top_p=sampler.top_p, min_p=sampler.min_p))
+                for t in range(logits.shape[0])]
 
     V = model.config.vocab_size
     plan = spec.plan.tolist() if spec.plan is not None else None
@@ -892,7 +962,9 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              use_graph: Optional[bool] = None, sync_every: int = 16, top_k: Optional[int] = None,
              seed: Optional[int] = None, device_loop: Optional[bool] = None,
              prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: int = 2, _spec_plan=None,
-             kv_cache_dtype: Optional[str] = None, prefill_chunk_size: Optional[int] = None, **_):
+             kv_cache_dtype: Optional[str] = None, prefill_chunk_size: Optional[int] = None,
+             repetition_penalty: Optional[float] = None, min_p: Optional[float] = None,
+             min_new_tokens: Optional[int] = None, **_):
     """Returns [B, prompt + generated] token ids (HF ``generate`` output convention).
 
     ``attention_mask`` [B, S] (bool / integer, HF semantics) batches prompts of unequal length: row
@@ -953,7 +1025,22 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     cache the tokens of chunk k attend to the QUANTISED rows of the chunks before it and of their
     own chunk (one flash kernel over the codes, no dequantised copy), so the logits differ from the
     whole-prompt prefill's by the quantisation error of the attention output. ``ValueError``: c < 1,
-    not an integer, or a padded ``attention_mask`` (a ragged prefill is one causal block)."""
+    not an integer, or a padded ``attention_mask`` (a ragged prefill is one causal block).
+
+    Logits processors (HF's names and order: they act on the logits before the temperature):
+    ``repetition_penalty`` = theta (None / 1.0: off): the logit x of every token in the row's prompt
+    (its masked tokens) or emitted so far becomes x / theta if x > 0, else x * theta; greedy is then
+    the argmax of the penalised logits. ``min_new_tokens`` = m (None / 0: off): the EOS ids count as
+    -inf while the row has fewer than m new tokens. ``min_p`` in (0, 1] (None / 0: off, sampling
+    only): after top-k / top-p, only the tokens whose probability is at least min_p times the most
+    likely one's stay, i.e. z_i >= z_max + ln(min_p). On the device loop all three run inside the
+    sampler kernel of the captured step (the seen set is a bitmap the kernel reads and extends);
+    the host loops apply ``_ref.sample_process`` / ``sample_tokens``, the same fp32 operations.
+    Every mode above takes them, except that prompt lookup takes ``min_p`` only: a verify row's seen
+    set and token number would have to include the drafts before it (a follow-up). ``ValueError``:
+    ``repetition_penalty`` <= 0, ``min_p`` outside [0, 1], ``min_new_tokens`` < 0 or >
+    ``max_new_tokens``, ``repetition_penalty`` != 1 or ``min_new_tokens`` > 0 with
+    ``prompt_lookup_num_tokens``."""
     was = model.training
     model.eval()
     try:
@@ -996,7 +1083,16 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
                                  f"prompt_lookup_num_tokens ({K}) exceeds max_position_embeddings ({limit}), the "
                                  "extent of the RoPE table")
         sampler = SamplerConfig(max_new_tokens=max_new_tokens, do_sample=do_sample, temperature=temperature, top_k=top_k,
-                                top_p=top_p, seed=seed, eos_ids=tuple(sorted(eos)), pad_id=pad_token_id)
+                                top_p=top_p, seed=seed, eos_ids=tuple(sorted(eos)), pad_id=pad_token_id,
+                                repetition_penalty=1.0 if repetition_penalty is None else float(repetition_penalty),
+                                min_p=float(min_p or 0.0) if do_sample else 0.0,
+                                min_new_tokens=int(min_new_tokens or 0))
+        if min_p is not None and not 0.0 <= float(min_p) <= 1.0:
+            raise ValueError(f"generate: min_p must be in [0, 1], got {min_p}")
+        _check_processors(sampler)
+        if K and (sampler.repetition_penalty != 1.0 or sampler.min_new_tokens > 0):
+            raise ValueError("generate: repetition_penalty / min_new_tokens with prompt_lookup_num_tokens: a verify "
+                             "row's seen set and token number would have to include the drafts before it")
         on_device = can and (device_loop if device_loop is not None else _DEVICE_SAMPLER)
         if K and max_new_tokens >= 1:
             new = _spec_generate(model, input_ids, rows, P, sampler, SpecConfig(K, N, _spec_plan), graph, on_device,
@@ -1032,8 +1128,8 @@ def _device_loop(model, input_ids, rows, P: int, sampler: SamplerConfig, sync_ev
     return dec.out[:, :done]
 
 
-def _multinomial_pick(logits, temperature: float, top_k: int, top_p: float, generator) -> torch.Tensor:
-    """A ``torch.multinomial`` draw per row after temperature, top-k and top-p, as HF chains them."""
+def _multinomial_pick(logits, temperature: float, top_k: int, top_p: float, generator, min_p: float = 0.0) -> torch.Tensor:
+    """A ``torch.multinomial`` draw per row after temperature, top-k, top-p and min_p, as HF chains them."""
     probs = torch.softmax(logits / temperature, -1)
     if 0 < top_k < probs.shape[-1]:
         kth = probs.topk(top_k, -1).values[..., -1:]
@@ -1044,6 +1140,8 @@ def _multinomial_pick(logits, temperature: float, top_k: int, top_p: float, gene
         keep = sp.cumsum(-1) - sp <= top_p
         sp = sp * keep
         probs = torch.zeros_like(probs).scatter(-1, si, sp)
+    if min_p > 0.0:
+        probs = torch.where(probs < min_p * probs.max(-1, keepdim=True).values, torch.zeros_like(probs), probs)
     return torch.multinomial(probs / probs.sum(-1, keepdim=True), 1, generator=generator).squeeze(-1)
 
 
@@ -1065,15 +1163,24 @@ def _host_loop(model, input_ids, rows, P: int, c: SamplerConfig, graph: bool, ge
     out = []
     finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
     all_done = []  # device flags: every row finished after token t
+    penalty = c.repetition_penalty != 1.0
+    seen = _seen_prompt(input_ids, rows, logits.shape[-1]).to(logits.device) if penalty else None
     for t in range(new):
+        sup = c.suppress(t)
         if c.do_sample and generator is None:
             # the device sampler's host implementation: token t draws the noise of counter t
             nxt = _ref.sample_tokens(logits, seed=c.seed, counter=t, temperature=c.temperature, top_k=c.top_k,
-                                     top_p=c.top_p)
+                                     top_p=c.top_p, seen=seen, suppress=sup, **c.processors)
         elif c.do_sample:
-            nxt = _multinomial_pick(logits, c.temperature, c.top_k, c.top_p, generator)
+            nxt = _multinomial_pick(_ref.sample_process(logits, c.repetition_penalty, seen, sup), c.temperature,
+                                    c.top_k, c.top_p, generator, c.min_p)
+        elif penalty or sup:
+            nxt = _ref.sample_tokens(logits, do_sample=False, repetition_penalty=c.repetition_penalty, seen=seen,
+                                     suppress=sup)
         else:
             nxt = logits.argmax(-1)
+        if penalty:  # the token a live row emits joins its seen set (a finished row emits the pad)
+            seen[torch.arange(B, device=seen.device), nxt] |= ~finished
         if c.pad_id is not None:
             nxt = torch.where(finished, torch.full_like(nxt, c.pad_id), nxt)
         out.append(nxt[:, None])

@@ -159,15 +159,62 @@ def sample_noise(seed: int, counter: int, B: int, V: int, device=None) -> torch.
     return -torch.log(-torch.log(u))
 
 
-def sample_filter(logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+def seen_words(V: int) -> int:
+    """Words per row of the sampler's seen bitmap: ceil(V / 32) rounded up to a multiple of 4."""
+    return ((V + 31) // 32 + 3) // 4 * 4
+
+
+def seen_to_bool(seen, V: int) -> torch.Tensor:
+    """``seen`` as bool [B, V]: itself, or the bits of the bitmap [B, seen_words(V)] (int32 / uint32
+    words; bit i & 31 of word i >> 5 is token i)."""
+    if seen.dtype == torch.bool:
+        return seen
+    i = torch.arange(V, device=seen.device)
+    words = seen.view(torch.int32)[:, i >> 5]
+    return ((words >> (i & 31)[None, :]) & 1).bool()
+
+
+def seen_from_bool(seen: torch.Tensor) -> torch.Tensor:
+    """bool [B, n] -> the bitmap's int32 words [B, seen_words(n)] (the inverse of ``seen_to_bool``)."""
+    B, n = seen.shape
+    W = seen_words(n)
+    bits = torch.zeros(B, W * 32, dtype=torch.long, device=seen.device)
+    bits[:, :n] = seen
+    words = (bits.view(B, W, 32) << torch.arange(32, device=seen.device)).sum(-1)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).int()
+
+
+def sample_process(logits, repetition_penalty: float = 1.0, seen=None, suppress=None) -> torch.Tensor:
+    """The sampler's logits processors, fp32 [B, V], with the kernel's fp32 operations: the ids in
+    ``suppress`` become -inf (``min_new_tokens``: the EOS ids while the row is too short); then, HF's
+    ``RepetitionPenaltyLogitsProcessor``, a ``seen`` token's logit x becomes x / theta if x > 0, else
+    x * theta (one fp32 operation by theta rounded to fp32; -inf stays -inf, NaN stays NaN and counts
+    as -inf later). ``seen``: bool [B, V], or the bitmap (``seen_to_bool``)."""
+    x = logits.float()
+    V = x.shape[-1]
+    if suppress is not None and len(suppress):
+        ids = torch.as_tensor(list(suppress), device=x.device)
+        x = x.index_fill(-1, ids[(ids >= 0) & (ids < V)], -math.inf)
+    if repetition_penalty != 1.0:
+        theta = torch.tensor(float(repetition_penalty), dtype=torch.float32, device=x.device)
+        x = torch.where(seen_to_bool(seen, V), torch.where(x > 0, x / theta, x * theta), x)
+    return x
+
+
+def sample_filter(logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                  repetition_penalty: float = 1.0, seen=None, min_p: float = 0.0, suppress=None):
     """The sampler's kept set, in float64 on z = fp32(logits) * fp32(1 / temperature) (the one
     fp32 multiply the kernel does; NaN counts as -inf). Returns (z [B, V] float64, keep [B, V] bool,
     frac [B, V] float64 = M_>(i) / Z, the top-p coordinate of every top-k survivor, inf elsewhere).
     top-k (0 or >= V: off) keeps i iff #{j : z_j > z_i} < k; top-p (1.0: off) keeps a survivor iff
     M_>(i) < top_p * Z, with e_j = exp(z_j - z_max), Z the survivors' sum and M_>(i) their sum over
-    z_j > z_i. Ties stay or go together, the maximum always stays, -inf never does."""
+    z_j > z_i. Ties stay or go together, the maximum always stays, -inf never does.
+    ``repetition_penalty`` / ``seen`` / ``suppress`` act on the logits first (``sample_process``).
+    ``min_p`` in (0, 1] (0: off; HF's ``MinPLogitsWarper``) also requires z_i >= z_max + ln(min_p):
+    ln in float64 rounded to fp32, then one fp32 add and a compare, as the kernel does them."""
     B, V = logits.shape
     inv_t = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(temperature), dtype=torch.float32)
+    logits = sample_process(logits, repetition_penalty, seen, suppress)
     z = (logits.float() * inv_t.to(logits.device)).double()
     z = torch.where(torch.isnan(z), torch.full_like(z, -math.inf), z)
     asc, order = z.sort(-1)
@@ -187,22 +234,28 @@ def sample_filter(logits, temperature: float = 1.0, top_k: int = 0, top_p: float
     frac = torch.where(keep & (z == zmax), torch.zeros_like(frac), frac)  # exactly 0 for the maximum
     if top_p < 1.0:
         keep = keep & (frac < top_p)
+    if min_p:
+        ln = torch.tensor(math.log(min_p), dtype=torch.float32, device=z.device)
+        keep = keep & (z >= (zmax.float() + ln).double())  # z holds fp32 values: the add is the kernel's
     return z, keep, frac
 
 
 def sample_tokens(logits, seed: int = 0, counter: int = 0, temperature: float = 1.0, top_k: int = 0,
-                  top_p: float = 1.0, do_sample: bool = True) -> torch.Tensor:
+                  top_p: float = 1.0, do_sample: bool = True, repetition_penalty: float = 1.0, seen=None,
+                  min_p: float = 0.0, suppress=None) -> torch.Tensor:
     """Host implementation (and oracle) of the device sampler: one token per row of logits [B, V],
-    int64 [B] on the logits' device. Greedy: argmax of the raw logits. Sampling: Gumbel-max,
+    int64 [B] on the logits' device. Greedy: argmax of the processed logits (``sample_process``: the
+    raw ones without a penalty or ``suppress``). Sampling: Gumbel-max,
     argmax over the kept set (``sample_filter``) of z_i + g_i with ``sample_noise(seed, counter)``.
     Lowest index on ties; index 0 when nothing is kept. The same (seed, counter) and the same
     logits give the same tokens as the kernel (up to fp32-vs-float64 near-ties)."""
     B, V = logits.shape
     if do_sample:
-        z, keep, _ = sample_filter(logits, temperature, top_k or 0, 1.0 if top_p is None else top_p)
+        z, keep, _ = sample_filter(logits, temperature, top_k or 0, 1.0 if top_p is None else top_p,
+                                   repetition_penalty, seen, min_p or 0.0, suppress)
         score = torch.where(keep, z + sample_noise(seed, counter, B, V, logits.device), torch.full_like(z, -math.inf))
     else:
-        score = logits.double()
+        score = sample_process(logits, repetition_penalty, seen, suppress).double()
         score = torch.where(torch.isnan(score), torch.full_like(score, -math.inf), score)
     best = score.max(-1, keepdim=True).values
     idx = torch.arange(V, device=logits.device).expand(B, V)
