@@ -875,6 +875,122 @@ bool lora_small_refresh(const std::vector<Tensor>& bs, const std::vector<int64_t
   return true;
 }
 
+// ------------------------------------------------------------------ DoRA (dora.hip)
+// Fills the per-target fields shared by the norm and the backward parameters; false when a target is
+// off the kernels' 16-row blocks. Malformed arguments raise.
+template <class P>
+static bool dora_targets_fill(P& p, const char* what, const std::vector<Tensor>& ms, const std::vector<int64_t>& offs,
+                              int64_t out) {
+  TORCH_CHECK(!ms.empty() && ms.size() <= (size_t)grt::kDoraMaxTargets && offs.size() == ms.size(), what, ": 1-4 targets");
+  p.targets = (int)ms.size();
+  for (size_t i = 0; i < ms.size(); ++i) {
+    const Tensor& m = ms[i];
+    TORCH_CHECK(m.is_cuda() && m.dim() == 1 && m.is_contiguous() && m.scalar_type() == at::kBFloat16, what,
+                ": magnitudes bf16 [n_i] on the GPU");
+    const int64_t n = m.size(0), off = offs[i];
+    TORCH_CHECK(off >= 0 && n >= 1 && off + n <= out, what, ": target inside [0, out)");
+    for (size_t j = 0; j < i; ++j)
+      TORCH_CHECK(off + n <= p.off[j] || p.off[j] + p.n[j] <= off, what, ": targets overlap");
+    if (off % 16 != 0 || n % 16 != 0) return false;
+    p.m[i] = m.data_ptr(), p.off[i] = (int)off, p.n[i] = (int)n;
+  }
+  return true;
+}
+
+// (c, norm) of one adapted module: c fp32 [out] = m / ||W + s B A|| row-wise on the targets' rows, 1
+// elsewhere; norm (want_norm) the norms. The weight is ``w`` (bf16 [out, in], any row stride) or the
+// NF4 codes ``q`` with fp32 ``absmax`` (blocksize 64). {} when the kernel does not take the shape.
+std::vector<Tensor> dora_norm(const optional<Tensor>& w, const optional<Tensor>& q, const optional<Tensor>& absmax,
+                              const std::vector<Tensor>& as, const std::vector<Tensor>& bs, const std::vector<Tensor>& ms,
+                              const std::vector<int64_t>& offs, int64_t out, double scaling, bool want_norm) {
+  TORCH_CHECK(w.has_value() != q.has_value() && q.has_value() == absmax.has_value(), "dora_norm: w, or q and absmax");
+  TORCH_CHECK(as.size() == ms.size() && bs.size() == ms.size() && !as.empty(), "dora_norm: one A, B, m per target");
+  TORCH_CHECK(as[0].dim() == 2, "dora_norm: A [r, in]");
+  const int64_t r = as[0].size(0), in = as[0].size(1);
+  TORCH_CHECK(out >= 1 && out <= INT32_MAX && in <= (1 << 30), "dora_norm: sizes");
+  grt::DoraNormParams p{};
+  if (!grt::dora_norm_supported((int)out, (int)in, (int)r) || !dora_targets_fill(p, "dora_norm", ms, offs, out)) return {};
+  for (size_t i = 0; i < as.size(); ++i) {
+    const Tensor &a = as[i], &b = bs[i];
+    TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.dim() == 2 && b.dim() == 2 && a.size(0) == r && a.size(1) == in &&
+                    b.size(0) == p.n[i] && b.size(1) == r, "dora_norm: A_i [r, in], B_i [n_i, r]");
+    if (a.scalar_type() != at::kBFloat16 || b.scalar_type() != at::kBFloat16 || !a.is_contiguous() || !b.is_contiguous() ||
+        reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 != 0)
+      return {};
+    p.a[i] = a.data_ptr(), p.b[i] = b.data_ptr();
+  }
+  const Tensor& dev = as[0];
+  if (w.has_value()) {
+    TORCH_CHECK(w->dim() == 2 && w->size(0) == out && w->size(1) == in && w->device() == dev.device(), "dora_norm: W [out, in]");
+    if (!rowmajor_bf16(*w) || w->stride(0) < in) return {};
+    p.w = w->data_ptr(), p.ldw = w->stride(0);
+  } else {
+    check_contig(*q, "qweight");
+    check_contig(*absmax, "absmax");
+    TORCH_CHECK(q->is_cuda() && absmax->is_cuda() && q->scalar_type() == at::kByte && absmax->scalar_type() == at::kFloat &&
+                    q->device() == dev.device() && absmax->device() == dev.device(), "dora_norm: qweight uint8, absmax fp32");
+    TORCH_CHECK(q->numel() * 2 == out * in && absmax->numel() * 64 == out * in, "dora_norm: nf4 shapes (blocksize 64)");
+    if (reinterpret_cast<uintptr_t>(q->data_ptr()) % 8 != 0) return {};
+    p.q = q->data_ptr<uint8_t>(), p.absmax = absmax->data_ptr<float>();
+  }
+  c10::OptionalDeviceGuard dg(dev.device());
+  const auto f32 = dev.options().dtype(at::kFloat);
+  Tensor g = at::empty({(int64_t)as.size(), r, r}, f32), c = at::empty({out}, f32), norm;
+  if (want_norm) norm = at::empty({out}, f32);
+  p.out = (int)out, p.in = (int)in, p.r = (int)r, p.scaling = (float)scaling;
+  p.g = g.data_ptr<float>(), p.c = c.data_ptr<float>(), p.norm = want_norm ? norm.data_ptr<float>() : nullptr;
+  grt::dora_norm(p, cur_stream(dev));
+  return want_norm ? std::vector<Tensor>{c, norm} : std::vector<Tensor>{c};
+}
+
+static void dora_check_rows(const char* what, const Tensor& t, int64_t M, int64_t N) {
+  TORCH_CHECK(rowmajor_bf16(t) && t.size(0) == M && t.size(1) == N && t.stride(0) >= N, what,
+              ": bf16 [tokens, out], unit column stride, 16-byte aligned rows");
+}
+
+// y [tokens, out] (bf16) *= c [out] (fp32) in place
+void dora_scale(Tensor& y, const Tensor& c) {
+  TORCH_CHECK(y.dim() == 2, "dora_scale: y [tokens, out]");
+  const int64_t M = y.size(0), N = y.size(1);
+  dora_check_rows("dora_scale", y, M, N);
+  check_contig(c, "c");
+  TORCH_CHECK(c.is_cuda() && c.scalar_type() == at::kFloat && c.numel() == N && N % 8 == 0 && N <= INT32_MAX &&
+                  c.device() == y.device(), "dora_scale: c fp32 [out], out % 8 == 0");
+  if (M == 0) return;
+  c10::OptionalDeviceGuard dg(y.device());
+  grt::dora_scale(y.data_ptr(), y.stride(0), c.data_ptr<float>(), M, (int)N, cur_stream(y));
+}
+
+// (du, dm): du = c (.) dy (bf16), dm fp32 [out] = sum_t dy y / m on the targets' columns, 0 elsewhere
+std::vector<Tensor> dora_scale_bwd(const Tensor& dy, const Tensor& y, const Tensor& c, const std::vector<Tensor>& ms,
+                                   const std::vector<int64_t>& offs) {
+  TORCH_CHECK(dy.dim() == 2 && dy.size(0) >= 1, "dora_scale_bwd: dy [tokens, out]");
+  const int64_t M = dy.size(0), N = dy.size(1);
+  dora_check_rows("dora_scale_bwd", dy, M, N);
+  dora_check_rows("dora_scale_bwd", y, M, N);
+  check_contig(c, "c");
+  TORCH_CHECK(c.is_cuda() && c.scalar_type() == at::kFloat && c.numel() == N && N % 8 == 0 && N <= INT32_MAX &&
+                  c.device() == dy.device() && y.device() == dy.device(), "dora_scale_bwd: c fp32 [out], out % 8 == 0");
+  grt::DoraBwdParams p{};
+  p.targets = (int)ms.size();
+  TORCH_CHECK(!ms.empty() && ms.size() <= (size_t)grt::kDoraMaxTargets && offs.size() == ms.size(), "dora_scale_bwd: 1-4 targets");
+  for (size_t i = 0; i < ms.size(); ++i) {
+    TORCH_CHECK(ms[i].is_cuda() && ms[i].dim() == 1 && ms[i].is_contiguous() && ms[i].scalar_type() == at::kBFloat16 &&
+                    offs[i] >= 0 && offs[i] + ms[i].size(0) <= N, "dora_scale_bwd: magnitudes bf16 [n_i] inside [0, out)");
+    p.m[i] = ms[i].data_ptr(), p.off[i] = (int)offs[i], p.n[i] = (int)ms[i].size(0);
+  }
+  c10::OptionalDeviceGuard dg(dy.device());
+  Tensor du = at::empty({M, N}, dy.options());
+  const auto f32 = dy.options().dtype(at::kFloat);
+  p.chunks = grt::dora_bwd_chunks(M, (int)N);
+  Tensor ws = at::empty({(int64_t)p.chunks, N}, f32), dm = at::empty({N}, f32);
+  p.dy = dy.data_ptr(), p.lddy = dy.stride(0), p.y = y.data_ptr(), p.ldy = y.stride(0);
+  p.du = du.data_ptr(), p.lddu = N, p.c = c.data_ptr<float>(), p.ws = ws.data_ptr<float>(), p.dm = dm.data_ptr<float>();
+  p.M = M, p.N = (int)N;
+  grt::dora_scale_bwd(p, cur_stream(dy));
+  return {du, dm};
+}
+
 // ------------------------------------------------------------------ cross entropy
 std::vector<Tensor> ce_fwd(const Tensor& logits, const Tensor& labels, int64_t ignore_index) {
   check_cuda(logits, "logits");
@@ -2360,6 +2476,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("offset"), py::arg("accumulate"));
   m.def("lora_small_refresh", &lora_small_refresh, py::arg("bs"), py::arg("offs"), py::arg("w"), py::arg("bt"),
         py::arg("col0"));
+  m.def("dora_norm", &dora_norm, py::arg("w"), py::arg("q"), py::arg("absmax"), py::arg("a"), py::arg("b"), py::arg("m"),
+        py::arg("offs"), py::arg("out"), py::arg("scaling"), py::arg("want_norm") = false);
+  m.def("dora_scale", &dora_scale, py::arg("y"), py::arg("c"));
+  m.def("dora_scale_bwd", &dora_scale_bwd, py::arg("dy"), py::arg("y"), py::arg("c"), py::arg("m"), py::arg("offs"));
   m.def("dropout_bwd_seeded", &dropout_bwd_seeded);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);

@@ -222,6 +222,33 @@ void lora_small_dx(const LoraDxParams& p, hipStream_t s);
 // lora_refresh for r % 8 == 0, r <= 32
 void lora_small_refresh(const LoraRefreshParams& p, hipStream_t s);
 
+// ---------------- DoRA (dora.hip) ----------------
+// c[j] = m[j] / ||W_j + s (B_i A_i)_j|| for the rows of every target i of one adapted module, 1 for
+// the other rows; W is bf16 [out][in] with row stride ldw, or (q != nullptr) NF4 codes + fp32 absmax
+// (blocksize 64). off_i % 16 == 0, n_i % 16 == 0; g is the fp32 workspace [targets][r][r] that
+// dora_norm fills with A_i A_i^T first; norm (optional) receives the norms.
+constexpr int kDoraMaxTargets = 4;
+struct DoraNormParams {
+  const void* w; int64_t ldw; const uint8_t* q; const float* absmax;
+  int out, in, r, targets; float scaling;
+  const void* a[kDoraMaxTargets]; const void* b[kDoraMaxTargets]; const void* m[kDoraMaxTargets];
+  int off[kDoraMaxTargets]; int n[kDoraMaxTargets];
+  float* g; float* c; float* norm;
+};
+bool dora_norm_supported(int out, int in, int r);
+void dora_norm(const DoraNormParams& p, hipStream_t s);
+// y [M][N] (bf16, row stride ldy) *= c [N] in place; N % 8 == 0
+void dora_scale(void* y, int64_t ldy, const float* c, int64_t M, int N, hipStream_t s);
+// du = c (.) dy and dm[j] = sum_t dy[t][j] y[t][j] / m[j] (columns of no target, or m[j] == 0: 0);
+// ws: fp32 [chunks][N] column partials, chunks = dora_bwd_chunks(M, N); no atomics
+struct DoraBwdParams {
+  const void* dy; int64_t lddy; const void* y; int64_t ldy; void* du; int64_t lddu;
+  const float* c; float* ws; float* dm; int64_t M; int N; int chunks; int64_t mchunk;
+  int targets; const void* m[kDoraMaxTargets]; int off[kDoraMaxTargets]; int n[kDoraMaxTargets];
+};
+int dora_bwd_chunks(int64_t M, int N);
+void dora_scale_bwd(const DoraBwdParams& p, hipStream_t s);
+
 // ---------------- attention (attention.hip) ----------------
 struct AttnParams {
   const void* q; const void* k; const void* v; void* o; float* lse;

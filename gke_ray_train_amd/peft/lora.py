@@ -28,6 +28,19 @@ Ranks: r % 64 == 0 runs lora.hip / lora_grad.hip, r = 8 / 16 / 32 runs lora_smal
 and the same direct-to-slot gradients); any other rank keeps the epilogue form on library GEMMs.
 
 Documented deviation: one dropout mask per fused input (HF draws separate masks for q, k, v).
+
+DoRA (``LoraConfig(use_dora=True)``, PEFT's weight-decomposed LoRA): every target gets a trainable
+``lora_magnitude_vector`` m [n_i], initialised to the row norms of its W rows, and the adapted output
+is y = c (.) u with u the LoRA output above and c_j = m_j / ||W_j + s (B_i A_i)_j||, the norm treated
+as a constant (detached) as in PEFT; rows of an untargeted slice keep c = 1. On MI355X c comes from
+csrc/kernels/dora.hip in one pass over the frozen weight as stored (bf16, or the NF4 codes: no bf16
+W, no [out, in] temporary), y is scaled in place, and the backward writes du = c (.) dy and
+dm_j = sum_t dy_tj y_tj / m_j in one pass (y is saved, not u; a row with m_j == 0 has y == 0 and gets
+dm_j = 0). Any shape the kernels do not take, and the CPU, evaluate the same three-term formula in
+fp32 torch. ``merged_weight`` folds c into the rows of W + s B A.
+Documented deviation: with ``lora_dropout`` > 0 in training PEFT recomputes the base product on the
+dropped input; here c scales the base output of the UNDROPPED input (the DoRA paper's form, no second
+base GEMM). With dropout 0 or in evaluation the two are identical.
 """
 from __future__ import annotations
 
@@ -59,6 +72,7 @@ class LoraConfig:
     modules_to_save: Optional[List[str]] = None
     init_lora_weights: bool = True
     use_rslora: bool = False
+    use_dora: bool = False
 
     @property
     def scaling(self) -> float:
@@ -134,6 +148,9 @@ _LORA_GRAD_KERNELS = os.environ.get("GRT_LORA_GRAD_KERNELS", "1") != "0"
 # csrc/kernels/lora_small.hip (16-wide rank tiles; the same switches select the fall-backs). Any other
 # rank that is not a multiple of 64 keeps ``_LoraFn`` on library GEMMs.
 _SMALL_RANKS = (8, 16, 32)
+# DoRA on csrc/kernels/dora.hip (norms from the stored weight, in-place scale, one-pass backward).
+# GRT_DORA_KERNELS=0: the fp32 torch evaluation of the same formula, also on the GPU.
+_DORA_KERNELS = os.environ.get("GRT_DORA_KERNELS", "1") != "0"
 
 
 def _bf16_cuda(*ts):
@@ -402,8 +419,34 @@ def _lora_dA(g, xd, As, order, r, C=None):
     return dAs
 
 
+class _DoraScaleFn(torch.autograd.Function):
+    """y = c (.) u in place over the LoRA output u (c fp32 [out], a constant); the backward reads dy and
+    the saved y once: du = c (.) dy and dm_j = sum_t dy_tj y_tj / m_j (dora.hip)."""
+
+    @staticmethod
+    def forward(ctx, u, c, offs, *mags):
+        _native.kernels().dora_scale(u.view(-1, u.shape[-1]), c)
+        ctx.mark_dirty(u)
+        ctx.offs = offs
+        ctx.save_for_backward(u, c, *mags)
+        return u
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, c, *mags = ctx.saved_tensors
+        n = y.shape[-1]
+        dy2 = dy.reshape(-1, n)
+        if dy2.dtype != y.dtype:
+            dy2 = dy2.to(y.dtype)
+        du, dm = _native.kernels().dora_scale_bwd(dy2.contiguous(), y.view(-1, n), c, [m.detach() for m in mags],
+                                                  ctx.offs)
+        return (du.view(dy.shape), None, None,
+                *[dm[off:off + m.shape[0]].to(m.dtype) for off, m in zip(ctx.offs, mags)])
+
+
 class LoraLinear(nn.Module):
-    """base(x) + scaling * B(dropout(A(x))) for every targeted (sub-)projection of ``base``."""
+    """base(x) + scaling * B(dropout(A(x))) for every targeted (sub-)projection of ``base``; with
+    ``use_dora`` the result is rescaled row-wise by magnitude / norm (module doc)."""
 
     def __init__(self, base: nn.Module, targets: List[tuple], cfg: LoraConfig):
         super().__init__()
@@ -431,6 +474,85 @@ class LoraLinear(nn.Module):
         self._wk_key = None  # (order, B versions, optimizer generation) the tail was last built from
         self._bt = None     # [R, out]: the B blocks transposed (adapter-gradient kernel), with W'
         self._acat = None   # (key, A_cat) of the decode branch when the A matrices are not adjacent
+        self.use_dora = bool(cfg.use_dora)
+        self._dora_c = None  # (key, c) of the forwards without autograd (decode), keyed like ``_acat``
+        if self.use_dora:
+            self.lora_magnitude_vector = nn.ParameterDict(
+                {name: nn.Parameter(torch.ones(n, device=dev, dtype=dt)) for name, _, n in self.targets})
+            with torch.no_grad():  # B = 0: the norm is ||W||
+                _, norm = self.dora_coefficients(want_norm=True)
+                for name, off, n in self.targets:
+                    self.lora_magnitude_vector[name].copy_(norm[off:off + n])
+
+    def _dora_tensors(self):
+        names = [t[0] for t in self.targets]
+        return ([self.lora_A[n].detach() for n in names], [self.lora_B[n].detach() for n in names],
+                [self.lora_magnitude_vector[n].detach() for n in names], [t[1] for t in self.targets])
+
+    @torch.no_grad()
+    def dora_coefficients(self, want_norm: bool = False):
+        """(c, norm): c fp32 [out] = m_j / ||W_j + s (B_i A_i)_j|| on the targets' rows and 1 on the
+        others; norm (``want_norm``, else None) the norms, 1 on untargeted rows. On the GPU one pass
+        of dora.hip over the stored weight (bf16 at its row stride, or NF4 codes + absmax); any other
+        shape, dtype or device: norm^2 = sum W^2 + 2 s b.(W A^T) + s^2 b^T (A A^T) b in fp32 torch."""
+        As, Bs, Ms, offs = self._dora_tensors()
+        b, s = self.base, self.scaling
+        if _DORA_KERNELS and _bf16_cuda(*As, *Bs, *Ms):
+            res = []
+            if isinstance(b, NF4Linear):
+                if b.blocksize == 64 and b.qweight.is_cuda and b.compute_dtype == torch.bfloat16:
+                    res = _native.kernels().dora_norm(None, b.qweight, b._absmax_f32(), As, Bs, Ms, offs,
+                                                      self.out_features, s, want_norm)
+            elif _bf16_cuda(b.weight):
+                res = _native.kernels().dora_norm(b.weight.detach(), None, None, As, Bs, Ms, offs, self.out_features,
+                                                  s, want_norm)
+            if res:
+                return res[0], (res[1] if want_norm else None)
+        w = _base_weight(b).detach()
+        c = torch.ones(self.out_features, device=w.device, dtype=torch.float32)
+        norm = torch.ones_like(c)
+        for a, bb, m, off in zip(As, Bs, Ms, offs):
+            wi, a, bb = w[off:off + m.shape[0]].float(), a.float(), bb.float()
+            n2 = (wi * wi).sum(1) + 2 * s * (bb * (wi @ a.t())).sum(1) + s * s * ((bb @ (a @ a.t())) * bb).sum(1)
+            norm[off:off + m.shape[0]] = n2.clamp_min(1e-30).sqrt()
+            c[off:off + m.shape[0]] = m.float() / norm[off:off + m.shape[0]]
+        return c, (norm if want_norm else None)
+
+    def _dora_cached_c(self):
+        """c of a forward without autograd, kept while A, B and m are unchanged (``_decode_acat``'s key
+        scheme; nothing cached under graph capture: the decoder's warm-up step fills the cache)."""
+        As, Bs, Ms, _ = self._dora_tensors()
+        key = (tuple((t.data_ptr(), t._version) for t in As + Bs + Ms), param_generation())
+        c = self._dora_c
+        if c is None or c[0] != key:
+            c = (key, self.dora_coefficients()[0])
+            if not (As[0].is_cuda and torch.cuda.is_current_stream_capturing()):
+                self._dora_c = c
+        return c[1]
+
+    def _dora(self, u):
+        """y = c (.) u over the LoRA output (in place on the GPU kernels' path)."""
+        mags = [self.lora_magnitude_vector[t[0]] for t in self.targets]
+        grad = torch.is_grad_enabled() and (u.requires_grad or any(m.requires_grad for m in mags))
+        kernels = (_DORA_KERNELS and _bf16_cuda(u, *mags) and u.is_contiguous() and self.out_features % 8 == 0
+                   and len(mags) <= 4 and u.data_ptr() % 16 == 0)
+        if not grad:
+            c = self._dora_cached_c()
+            if kernels:
+                _native.kernels().dora_scale(u.view(-1, self.out_features), c)
+                return u
+            return (u.float() * c).to(u.dtype)
+        if kernels:
+            if u._is_view():  # ``_LoraFn`` hands out a view of its y: autograd forbids scaling that in place
+                u = u.clone()
+            return _DoraScaleFn.apply(u, self.dora_coefficients()[0], [t[1] for t in self.targets], *mags)
+        _, norm = self.dora_coefficients(want_norm=True)  # a constant; m's gradient flows through c
+        pieces, pos = [], 0
+        for (_, off, n), m in sorted(zip(self.targets, mags), key=lambda tm: tm[0][1]):
+            pieces += [norm.new_ones(off - pos), m.float()]
+            pos = off + n
+        pieces.append(norm.new_ones(self.out_features - pos))
+        return (u.float() * (torch.cat(pieces) / norm)).to(u.dtype)
 
     @property
     def kcat_pad(self) -> int:
@@ -596,6 +718,10 @@ class LoraLinear(nn.Module):
         return list(self.lora_A.values()) + list(self.lora_B.values())
 
     def forward(self, x):
+        u = self._lora_forward(x)
+        return self._dora(u) if self.use_dora else u
+
+    def _lora_forward(self, x):
         if x.is_cuda:
             p = self.dropout_p if self.training else 0.0
             seed, offset = ops.fused.dropout_seed_offset(x) if p > 0 else (0, 0)
@@ -631,6 +757,12 @@ class LoraLinear(nn.Module):
     def merged_weight(self) -> torch.Tensor:
         w = self.base.dequantize() if isinstance(self.base, NF4Linear) else self.base.weight.detach().clone()
         w = w.clone()
+        if self.use_dora:  # c (.) (W + s B A) row-wise, rounded once
+            c = self.dora_coefficients()[0]
+            for n, off, cnt in self.targets:
+                wi = w[off:off + cnt].float() + self.lora_B[n].float() @ self.lora_A[n].float() * self.scaling
+                w[off:off + cnt] = (wi * c[off:off + cnt, None]).to(w.dtype)
+            return w
         for n, off, cnt in self.targets:
             w[off:off + cnt] += (self.lora_B[n].float() @ self.lora_A[n].float() * self.scaling).to(w.dtype)
         return w
@@ -721,6 +853,9 @@ class PeftModel(nn.Module):
                 key = f"{base}.{sub}" if getattr(m.base, "slices", None) else full
                 out[f"base_model.model.{key}.lora_A.weight"] = m.lora_A[sub].detach().contiguous()
                 out[f"base_model.model.{key}.lora_B.weight"] = m.lora_B[sub].detach().contiguous()
+                if m.use_dora:
+                    out[f"base_model.model.{key}.lora_magnitude_vector"] = \
+                        m.lora_magnitude_vector[sub].detach().contiguous()
         return out
 
     def load_adapter_state_dict(self, sd: Dict[str, torch.Tensor]):
@@ -731,6 +866,11 @@ class PeftModel(nn.Module):
                     key = f"{base}.{sub}" if getattr(m.base, "slices", None) else full
                     m.lora_A[sub].copy_(sd[f"base_model.model.{key}.lora_A.weight"])
                     m.lora_B[sub].copy_(sd[f"base_model.model.{key}.lora_B.weight"])
+                    if m.use_dora:
+                        mk = f"base_model.model.{key}.lora_magnitude_vector"
+                        if mk not in sd:
+                            raise KeyError(f"DoRA model, but the adapter has no {mk} (saved without use_dora?)")
+                        m.lora_magnitude_vector[sub].copy_(sd[mk])
 
     def save_pretrained(self, path: str):
         from safetensors.torch import save_file

@@ -68,6 +68,7 @@ class FineTuneConfig:
     MAX_STEPS: int = -1
     GRADIENT_CHECKPOINTING: bool = False
     USE_LORA_BF16: bool = False         # BASELINE config #4: LoRA on an unquantized bf16 base
+    USE_DORA: bool = False              # LoraConfig(use_dora=True): weight-decomposed LoRA (peft/lora.py)
     SEED: int = 0
 
 

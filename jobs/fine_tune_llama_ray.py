@@ -126,7 +126,8 @@ def train_loop_per_worker(config: dict):
                                                   bnb_4bit_use_double_quant=config["USE_NESTED_QUANT"]))
     if config["USE_QLORA"] or config.get("USE_LORA_BF16"):
         lora = LoraConfig(lora_alpha=config["LORA_ALPHA"], lora_dropout=config["LORA_DROPOUT"], r=config["LORA_R"],
-                          bias="none", task_type="CAUSAL_LM", target_modules=config["LLAMA_TARGET_MODULES"])
+                          bias="none", task_type="CAUSAL_LM", target_modules=config["LLAMA_TARGET_MODULES"],
+                          use_dora=bool(config.get("USE_DORA", False)))
     n_train, n_eval = config.get("NUM_TRAIN_SAMPLES", 1000), config.get("NUM_EVAL_SAMPLES", 200)
     train_rows = synthetic_text_to_sql(max(n_train, 1), seed=42, split="train")
     eval_rows = synthetic_text_to_sql(max(n_eval, 1), seed=42, split="test")
